@@ -10,7 +10,10 @@ GOP, and after EVERY call the two f-strings the script prints, which look at tha
 Every pair is therefore finished (files written, sizes known) before the next call starts.  The model is in its default
 mode: finished tensors and Python floats per call; from the second pair of a configuration on it replays captured
 launch plans (HIP graphs, luma / chroma coders of the pair on two streams, pMCTF.hip.pair_plan).
-In the same run, after the timed region, rank 0 also measures (auxiliary figures, never `value`):
+A plain run sets up, warms up, times exactly --steps steps, writes the last step's outputs when --dump-outputs DIR is
+given (dump_outputs) and prints the line: `value`, `ms_per_step`, bpp and the configuration.  Everything below is
+measured and checked only with --full.
+With --full, after the timed region, rank 0 also measures (auxiliary figures, never `value`):
   * `roofline` / `stream_launches_single_stream` — the same loop with the plans off: plain stream launches on ONE
                           stream, the dominant convolution bracketed by HIP events on that stream (with the plans on,
                           luma and chroma kernels share the GPU, which per-kernel events cannot separate);
@@ -28,16 +31,18 @@ N GPUs encode N independent GOPs (closed GOPs are independent units: no data-pat
 `value`; with N > 1 the same ranks then time the north-star layout as `pair_sharded`: ONE GOP, the pairs of each
 temporal stage spread over the ranks, motion context relayed rank to rank, one all-gather of the subband tree per
 stage over RCCL (strong scaling), alone and — from three ranks on — with max(2, N/2) closed GOPs in flight.
-That block runs after the timed region and its roofline pass and under a watchdog (--pair_shard_timeout_s): a rank that
-dies or a collective that never completes costs the block, never the line.
+That block (--full only) runs after the timed region and its roofline pass and under a watchdog
+(--pair_shard_timeout_s): a rank that dies or a collective that never completes costs the block, never the line.
 Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
+import atexit
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -48,7 +53,45 @@ sys.path.insert(0, os.path.join(ROOT, "learned-pmctf_amd"))
 
 # work of one 1080p pair in GMAC: coded frame 10 186, SpyNet 707, MV codec 163, temporal P+U 32.5
 _W_FRAME, _W_MOTION = 10186.0, 707.0 + 163.0 + 32.5
-PEAK_F32_MFMA = 157.3          # TFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md "Peak FP32 (matrix)"
+PEAK_F32_MFMA = 157.3          # TFLOP/s, MI355X peak FP32 (matrix)
+DUMP_BYTES = 64_000_000        # --dump-outputs writes at most this much
+
+
+def scratch_dir(prefix):
+    """a folder for the bitstreams of the run, removed when the process exits"""
+    d = tempfile.mkdtemp(prefix=prefix)
+    atexit.register(shutil.rmtree, d, True)
+    return d
+
+
+def dump_outputs(folder, enc, bin_folder):
+    """--dump-outputs DIR: what a caller of the timed path received from its last step, one float32 / float64 .npy per
+    array: bits and motion bits per frame, the coded tree of every frame (frames_coded of pmctf_gop.encode_gop: luma and
+    chroma subbands, decoded motion) and the bitstream files of that step (their sizes, and their bytes concatenated in
+    name order).  Frames and weights come from fixed seeds, so two builds run with the same arguments can be compared
+    file for file.  An array larger than its share of DUMP_BYTES is written as a fixed sample of its flattened elements
+    (seeded by its name: the same indices in every run)."""
+    import zlib
+    import numpy as np
+    arrays = {"bits": np.asarray(enc["bits"], dtype=np.float64), "bits_mv": np.asarray(enc["bits_mv"], dtype=np.float64)}
+    for i, coded in enumerate(enc["frames_coded"]):
+        for part, t in zip(("y", "c", "mv"), coded):
+            if t is not None:
+                arrays[f"frame{i:02d}_{part}"] = t.detach().float().cpu().numpy()
+    blobs = []
+    for n in sorted(os.listdir(bin_folder)):
+        with open(os.path.join(bin_folder, n), "rb") as f:
+            blobs.append(f.read())
+    arrays["bitstream_sizes"] = np.array([len(b) for b in blobs], dtype=np.float64)
+    arrays["bitstream_bytes"] = np.frombuffer(b"".join(blobs), dtype=np.uint8).astype(np.float32)
+    share = (DUMP_BYTES - 4096 * len(arrays)) // len(arrays)     # bytes per array; an .npy header takes less than 4 KB
+    os.makedirs(folder, exist_ok=True)
+    for name, a in arrays.items():
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def cpu_baseline(width, height, gop, q_index):
@@ -165,7 +208,14 @@ def main():
     ap.add_argument("--pair_shard_steps", type=int, default=2, help="steps of the `pair_sharded` block (N > 1; 0 to skip)")
     ap.add_argument("--overlap_gops", type=int, default=0,
                     help="closed GOPs in flight in the `pair_sharded` block's overlapped variant (SURVEY 8e)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0; dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own figures, also measure and check everything else: PSNR and parity against "
+                         "the reference's digests, roofline pass, pair_sharded block, cpu_baseline, the auxiliary legs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))
@@ -221,12 +271,12 @@ def main():
         return stride == 1 and (not conv.small) and conv.Cin == 112 and conv.Cout == 112 and conv.KH == 3 and \
             x.shape[1] == sub_h and x.shape[2] == sub_w
 
-    tmp = tempfile.mkdtemp(prefix=f"pmctf_bench_r{rank}_")
+    tmp = scratch_dir(f"pmctf_bench_r{rank}_")
     last = {}
     extra = []      # --inflight > 1: further GOPs of the synthetic sequence, each with its own stream and output folder
     for k in range(1, args.inflight):
         extra.append((gop_frames(1234 + rank + 1000 * k), torch.cuda.Stream(device=dev),
-                      tempfile.mkdtemp(prefix=f"pmctf_bench_r{rank}_g{k}_")))
+                      scratch_dir(f"pmctf_bench_r{rank}_g{k}_")))
 
     def code_extra(fr, stream, folder):
         torch.cuda.set_device(dev)
@@ -260,14 +310,13 @@ def main():
             dist.barrier()
 
     def timed(fn, steps, warmup, probe_kernels=False, collective=True):
-        """W untimed steps, then exactly K steps bracketed by barrier + synchronize; convolutions of the dominant shape
-        that go through stream launches inside the timed region are bracketed by HIP events on the launch stream"""
+        """W untimed steps, then exactly K steps bracketed by barrier + synchronize; with probe_kernels, convolutions of
+        the dominant shape that go through stream launches inside the timed region are bracketed by HIP events on the
+        launch stream"""
         for _ in range(warmup):
             fn()
         sync(collective)
-        probe = {"match": dominant, "events": []}
-        if probe_kernels:
-            probe["kernels"] = {}
+        probe = {"match": dominant, "events": [], "kernels": {}} if probe_kernels else None
         ops.CONV_PROBE = probe
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -297,8 +346,8 @@ def main():
 
     if rank == 0:
         enc = last["enc"]
-        rec = pmctf_gop.decode_gop(net, [list(f) for f in enc["frames_coded"]])
-        ps = pmctf_gop.gop_psnr(rec, frames, H, W)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, enc, tmp)
         headline = (W, H, args.gop, args.q_index) == (1920, 1080, 16, 3)
         out = {
             "metric": "encoded 1080p frames/sec (GOP=16, q_index=3)" if headline
@@ -316,8 +365,18 @@ def main():
                        "parallelism": f"gop-dp{world}" if args.shard == "gops" else f"pair-shard{world}",
                        "weights": "deterministic synthetic (pmctf_synth seed 0)"},
             "bpp": sum(enc["bits"]) / (args.gop * W * H),
-            "psnr_yuv": sum(p["yuv"] for p in ps) / len(ps),
         }
+    if not args.full:
+        if rank == 0:
+            out["bench_wall_s"] = time.time() - t_process
+            print(json.dumps(out), flush=True)
+        leave_group(dist)
+        return
+
+    if rank == 0:
+        rec = pmctf_gop.decode_gop(net, [list(f) for f in enc["frames_coded"]])
+        ps = pmctf_gop.gop_psnr(rec, frames, H, W)
+        out["psnr_yuv"] = sum(p["yuv"] for p in ps) / len(ps)
         # "+ bpp/PSNR parity vs CPU ref" of BASELINE's metric: rank 0 codes exactly the sequence the real reference was
         # run on (tools/make_golden.py --width 1920 --height 1080 --gop_only --gop 16 --me_stages 4 [--q_index q]);
         # compare with the digests of that run (data, tests/golden/).
@@ -444,7 +503,7 @@ def main():
             G2 = args.overlap_gops if args.overlap_gops > 0 else max(2, world // 2)
             if G2 > 1 and world >= 3:     # with two ranks the GOPs would be coded one after the other
                 gops = [frames0] + [gop_frames(1234 + 1000 * k) for k in range(1, G2)]
-                folders = [tmp] + [tempfile.mkdtemp(prefix=f"pmctf_bench_r{rank}_o{k}_") for k in range(1, G2)]
+                folders = [tmp] + [scratch_dir(f"pmctf_bench_r{rank}_o{k}_") for k in range(1, G2)]
 
                 def overlapped():
                     last["po"] = pmctf_dist.encode_gops_pair_sharded_overlapped(net, gops, H, W, args.q_index, folders,
@@ -518,7 +577,7 @@ def main():
         if aux and K > 1 and hasattr(pmctf_gop, "encode_gops_batched"):
             def cross_gop():
                 gops = [frames] + [gop_frames(1234 + 1000 * k) for k in range(1, K)]
-                folders = [tmp] + [tempfile.mkdtemp(prefix=f"pmctf_bench_x{k}_") for k in range(1, K)]
+                folders = [tmp] + [scratch_dir(f"pmctf_bench_x{k}_") for k in range(1, K)]
 
                 def cross():
                     last["encs"] = pmctf_gop.encode_gops_batched(net, gops, H, W, args.q_index, folders)
@@ -618,16 +677,21 @@ def main():
             out["aux_skipped_over_budget"] = skipped
         out["bench_wall_s"] = time.time() - t_process
         print(json.dumps(out), flush=True)
-    if dist is not None:
-        import threading
-        leave = threading.Timer(60.0, lambda: os._exit(3))      # the line is out; a barrier that never returns is a failure
-        leave.daemon = True
-        leave.start()
-        try:
-            dist.barrier()
-            dist.destroy_process_group()
-        except Exception:  # noqa: BLE001 - a rank that left through its watchdog
-            pass
+    leave_group(dist)
+
+
+def leave_group(dist):
+    if dist is None:
+        return
+    import threading
+    leave = threading.Timer(60.0, lambda: os._exit(3))      # the line is out; a barrier that never returns is a failure
+    leave.daemon = True
+    leave.start()
+    try:
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception:  # noqa: BLE001 - a rank that left through its watchdog
+        pass
 
 
 if __name__ == "__main__":

@@ -1072,13 +1072,13 @@ def test_headline_config_stage_batched_vs_reference(cuda, gop):
 
 
 def test_bench_contract_small_run(cuda):
-    """bench.py prints ONE JSON line with the driver's fields (exercised on a tiny GOP so that it takes seconds)"""
+    """bench.py --full prints ONE JSON line with the driver's fields (exercised on a tiny GOP so that it takes seconds)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--width", "256", "--height", "128", "--gop", "4",
-                          "--steps", "1", "--warmup", "1", "--no_cpu_baseline"], capture_output=True, text=True,
+                          "--steps", "1", "--warmup", "1", "--no_cpu_baseline", "--full"], capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1091,6 +1091,42 @@ def test_bench_contract_small_run(cuda):
     assert j["dtype"] == "f32" and j["data"] == "synthetic" and "workload" in j["config"] and j["value"] > 0
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in j["roofline"], k
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(cuda):
+    """a plain bench.py run (no --full): exactly --steps timed steps, the line's fields, nothing of the --full legs; with
+    --dump-outputs the last step's bits, coded tree and bitstreams as float32 / float64 .npy within 64 MB, the same in
+    two runs with the same arguments"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as td:
+        dumps = []
+        for run in ("a", "b"):
+            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--width", "256", "--height", "128",
+                                  "--gop", "4", "--steps", "2", "--warmup", "1", "--dump-outputs", os.path.join(td, run)],
+                                 capture_output=True, text=True, timeout=600)
+            assert out.returncode == 0, out.stderr[-2000:]
+            lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+            assert len(lines) == 1
+            j = json.loads(lines[0])
+            for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+                assert k in j, k
+            assert j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "frames/s" and j["dtype"] == "f32"
+            assert j["ms_per_step"] > 0 and abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+            for k in ("roofline", "cpu_baseline", "psnr_yuv", "stage_batched", "aux_profiles", "hbm_kernels"):
+                assert k not in j, k
+            folder = os.path.join(td, run)
+            names = sorted(os.listdir(folder))
+            assert sum(os.path.getsize(os.path.join(folder, n)) for n in names) <= 64_000_000
+            dumps.append({n: np.load(os.path.join(folder, n)) for n in names})
+        a, b = dumps
+        assert {"bits.npy", "bits_mv.npy", "bitstream_sizes.npy", "bitstream_bytes.npy", "frame00_y.npy", "frame00_c.npy",
+                "frame01_mv.npy"} <= set(a)
+        assert a["bits.npy"].shape == (4,) and a["bitstream_sizes.npy"].shape == (3 * (4 - 1) + 2,)
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        assert a.keys() == b.keys() and all(np.array_equal(a[n], b[n]) for n in a)
 
 
 @pytest.mark.parametrize("gop,size", [(2, (128, 128)), (32, (128, 128)), (4, (200, 120))])

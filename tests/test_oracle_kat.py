@@ -51,20 +51,24 @@ def test_rans_known_answer_stream_and_roundtrip():
 
 
 def test_reference_ops_cpp_agrees_when_built():
-    """oracle/_ref holds the reference's own ops.cpp (built in the build container only)."""
+    """The reference's own pmf_to_quantized_cdf (its ops.cpp) against the oracle's: on the CDFs it wrote for four
+    pmfs (tests/golden/reference_pmf_to_quantized_cdf.npz), and live where oracle/_ref is built from the reference."""
     import glob, importlib.util, os
     from pmctf_oracle import clib
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pmf_to_quantized_cdf.npz"))
     so = glob.glob(os.path.join(os.path.dirname(clib.__file__), "..", "_ref", "MLCodec_CXX*.so"))
-    if not so:
-        import pytest
-        pytest.skip("oracle/_ref not built here")
-    spec = importlib.util.spec_from_file_location("MLCodec_CXX", so[0])
-    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+    m = None
+    if so:
+        spec = importlib.util.spec_from_file_location("MLCodec_CXX", so[0])
+        m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
     rng = np.random.default_rng(0)
     for n in (3, 7, 40, 101):
         p = rng.random(n).astype(np.float32) ** 4
         p /= p.sum()
-        assert list(m.pmf_to_quantized_cdf(p.tolist(), 16)) == clib.pmf_to_quantized_cdf(p).tolist()
+        assert np.array_equal(p, g[f"pmf_{n}"])
+        assert clib.pmf_to_quantized_cdf(p).tolist() == g[f"cdf_{n}"].tolist()
+        if m is not None:
+            assert list(m.pmf_to_quantized_cdf(p.tolist(), 16)) == g[f"cdf_{n}"].tolist()
 
 
 def test_synthetic_sequences_are_pinned():

@@ -579,3 +579,41 @@ def test_capture_gate_excludes_other_threads_while_recording():
             assert inside is None or inside == name, log
     assert sum(1 for _, w in log if w == "rec+") == 6
 
+
+
+def test_bench_dump_outputs_types_budget_and_sample(monkeypatch):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array the timed path hands back (bits, coded tree of every
+    frame, the bitstream files), within the byte budget; an array over its share is a fixed sample, the same every run."""
+    import bench
+    rng = np.random.default_rng(3)
+    y = torch.from_numpy(rng.standard_normal((1, 1, 64, 96)).astype(np.float32))
+    c = torch.from_numpy(rng.standard_normal((2, 1, 32, 48)).astype(np.float32))
+    mv = torch.from_numpy(rng.standard_normal((1, 2, 16, 24)).astype(np.float32))
+    enc = {"bits": [1234.0, 56.0], "bits_mv": [0.0, 7.0], "frames_coded": [[y, c, None], [y * 2, c * 2, mv]]}
+    with tempfile.TemporaryDirectory() as td:
+        bins = os.path.join(td, "bins")
+        os.makedirs(bins)
+        for name, n in (("1.bin", 300), ("1.bin_c", 40)):
+            with open(os.path.join(bins, name), "wb") as f:
+                f.write(rng.integers(0, 256, n, dtype=np.uint8).tobytes())
+
+        def dump(folder):
+            bench.dump_outputs(os.path.join(td, folder), enc, bins)
+            files = sorted(os.listdir(os.path.join(td, folder)))
+            return {n: np.load(os.path.join(td, folder, n)) for n in files}, \
+                sum(os.path.getsize(os.path.join(td, folder, n)) for n in files)
+
+        whole, _ = dump("whole")
+        assert sorted(whole) == ["bits.npy", "bits_mv.npy", "bitstream_bytes.npy", "bitstream_sizes.npy", "frame00_c.npy",
+                                 "frame00_y.npy", "frame01_c.npy", "frame01_mv.npy", "frame01_y.npy"]
+        assert all(a.dtype in (np.float32, np.float64) for a in whole.values())
+        assert whole["bits.npy"].tolist() == enc["bits"] and whole["bitstream_sizes.npy"].tolist() == [300, 40]
+        assert np.array_equal(whole["frame01_mv.npy"], mv.numpy()) and np.array_equal(whole["frame00_y.npy"], y.numpy())
+        monkeypatch.setattr(bench, "DUMP_BYTES", 9 * 4096 + 9 * 4000)      # every array gets 4000 bytes
+        a, size_a = dump("a")
+        b, _ = dump("b")
+        assert size_a <= bench.DUMP_BYTES
+        assert a["frame00_y.npy"].shape == (1000,) and a["bits.npy"].shape == (2,)
+        flat = y.numpy().reshape(-1)
+        assert np.isin(a["frame00_y.npy"], flat).all() and len(np.unique(a["frame00_y.npy"])) == 1000
+        assert all(np.array_equal(a[n], b[n]) for n in a)

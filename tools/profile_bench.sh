@@ -7,7 +7,7 @@ out=$R/gpurun_out/$1
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_bench
-rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o bench --output-format csv -- python3 $R/bench.py --steps 1 --no_aux --no_cpu_baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o bench --output-format csv -- python3 $R/bench.py --steps 1 --full --no_aux --no_cpu_baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
 cp /tmp/prof_bench/bench_kernel_stats.csv $out/bench_kernel_stats.csv
 python3 - <<PY > $out/dominant_kernel_trace.txt
 import csv, statistics
@@ -21,7 +21,7 @@ def line(name, part):
     ds = [d(r) for r in part]
     if ds:
         print(f"  {name}: {len(ds)} launches, mean {statistics.mean(ds):.1f} us, median {statistics.median(ds):.1f} us, min {min(ds):.1f}, max {max(ds):.1f}")
-print(f"kernel trace of: python3 bench.py --steps 1 --no_aux --no_cpu_baseline   ({len(rows)} kernel launches)")
+print(f"kernel trace of: python3 bench.py --steps 1 --full --no_aux --no_cpu_baseline   ({len(rows)} kernel launches)")
 print("dominant convolution, 3x3 112->112 on ONE 576x960 plane")
 n = 57 * 16                # the roofline pass codes one GOP through stream launches: 57 such convolutions per coded luma frame
 line("stream launches, first pair of every configuration in the warm-up GOP (whole rounds: conv3x3s1_wave_kernel<7,2> grid 2040x256)", cut[:-n])
