@@ -236,7 +236,7 @@ __global__ __launch_bounds__(128 * LL_MAX_PLANES) void ll_ar_decode_kernel(LLArg
                     const float mean = prm[pl][1];
                     s = s < 1e-5f ? 1e-5f : s;
                     float iv = (pm::logf_(s) - a.lmin) / a.lstep;
-                    iv = iv >= 0.0f ? iv : 0.0f;          // also maps NaN (corrupt stream) to row 0
+                    iv = iv >= 0.0f ? iv : 0.0f;          // a NaN scale (corrupt stream) still gives a row in 0..255
                     iv = iv > 255.0f ? 255.0f : iv;
                     const int row = (int)iv;
                     const int32_t *cd = a.cdf + (long)row * a.cols;
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(NF) void ll_ar_stream_kernel(LLArgs a) {
                     const float mean = l_prm[pl * 2 + 1];
                     s = s < 1e-5f ? 1e-5f : s;
                     float iv = (pm::logf_(s) - a.lmin) / a.lstep;
-                    iv = iv >= 0.0f ? iv : 0.0f;          // also maps NaN (corrupt stream) to row 0
+                    iv = iv >= 0.0f ? iv : 0.0f;          // a NaN scale (corrupt stream) still gives a row in 0..255
                     iv = iv > 255.0f ? 255.0f : iv;
                     const int row = (int)iv;
                     const int32_t *cd = l_cdf + row * a.cols;
@@ -879,7 +879,7 @@ __global__ __launch_bounds__(NF) void ll_ar_row_kernel(LLArgs a, int h) {
                 const float mean = l_prm[pl * 2 + 1];
                 s = s < 1e-5f ? 1e-5f : s;
                 float iv = (pm::logf_(s) - a.lmin) / a.lstep;
-                iv = iv >= 0.0f ? iv : 0.0f;              // also maps NaN (corrupt stream) to row 0
+                iv = iv >= 0.0f ? iv : 0.0f;              // a NaN scale (corrupt stream) still gives a row in 0..255
                 iv = iv > 255.0f ? 255.0f : iv;
                 const int row = (int)iv;
                 const int32_t *cd = l_cdf + row * a.cols;
@@ -1184,7 +1184,7 @@ __device__ __forceinline__ void ll_ar_row2_body(const LLArgs &a, const int h, fl
                 const float mean = l_prm[pl * 2 + 1];
                 s = s < 1e-5f ? 1e-5f : s;
                 float iv = (pm::logf_(s) - a.lmin) / a.lstep;
-                iv = iv >= 0.0f ? iv : 0.0f;              // also maps NaN (corrupt stream) to row 0
+                iv = iv >= 0.0f ? iv : 0.0f;              // a NaN scale (corrupt stream) still gives a row in 0..255
                 iv = iv > 255.0f ? 255.0f : iv;
                 const int row = (int)iv;
                 const int32_t *cd = l_cdf + row * a.cols;
@@ -1256,9 +1256,9 @@ __global__ __launch_bounds__(2 * NF) void ll_ar_row2_kernel(LLArgs a, int h) {
 
 // four-step decompress: CDF rows of step k (0 off the mask), then x_hat at the mask positions
 __device__ __forceinline__ int scale_index(float s, float lmin, float step) {
-    s = s < 1e-5f ? 1e-5f : s;
+    s = s >= 1e-5f ? s : 1e-5f;    // max(s, 1e-5); also maps NaN (corrupt stream) to row 0: pm::logf_(NaN) is finite
     float v = (pm::logf_(s) - lmin) / step;
-    v = v >= 0.0f ? v : 0.0f;      // also maps NaN (corrupt stream) to row 0
+    v = v >= 0.0f ? v : 0.0f;
     v = v > 255.0f ? 255.0f : v;
     return (int)v;
 }

@@ -303,9 +303,9 @@ __global__ void lstm_gates_kernel(const float *__restrict__ xh, const float *__r
 
 // GaussianEncoder.build_indexes (entropy_models.py:269-273) in PM-F32
 __device__ __forceinline__ int scale_index(float s, float lmin, float step) {
-    s = s < 1e-5f ? 1e-5f : s;   // torch.maximum(scales, 1e-5)
+    s = s >= 1e-5f ? s : 1e-5f;  // torch.maximum(scales, 1e-5); NaN -> 1e-5, row 0 (pm::logf_(NaN) is finite)
     float v = (pm::logf_(s) - lmin) / step;
-    v = v >= 0.0f ? v : 0.0f;      // also maps NaN to row 0 instead of an out-of-range row
+    v = v >= 0.0f ? v : 0.0f;
     v = v > 255.0f ? 255.0f : v;
     return (int)v;
 }

@@ -503,3 +503,58 @@ def test_lstm_gates_with_aten_thread_tails(cuda):
         hid, cn = ops.lstm_gates(nhwc(np.concatenate(xs)), nhwc(np.concatenate(cells)), ref_planes=n_ref, aten_threads=8)
         assert_same(hid.permute(0, 3, 1, 2).cpu().numpy(), np.concatenate([r[0] for r in refs]), "hidden, stacked batch")
         assert_same(cn.permute(0, 3, 1, 2).cpu().numpy(), np.concatenate([r[1] for r in refs]), "cell, stacked batch")
+
+
+def test_scale_index_rows_at_every_gpu_site(cuda):
+    """Every GPU site that selects a CDF row from a scale (decode: fourstep_indexes, mv_fourpart_indexes; encode:
+    fourstep_quant, ll_quant, mv_fourpart) against the reference formula's rows at +-64 ulps of each of the 255 row
+    boundaries and on the special values (tests/golden/reference_scale_index_boundaries.npz), against the oracle on 10^6
+    log-uniform scales in [1e-6, 1e3], and NaN to row 0."""
+    from helpers import golden
+    from pmctf_oracle import entropy
+    from pMCTF.hip import ops
+    g = entropy.GaussianTables()
+    lmin, lstep = g.log_scale_min, g.log_scale_step
+    d = golden("reference_scale_index_boundaries.npz")
+    rnd = np.exp(_rng(11).uniform(np.log(1e-6), np.log(1e3), 10 ** 6)).astype(np.float32)
+    sets = [("fixture", d["scale_x"], d["scale_row"].astype(np.int16)),
+            ("log-uniform", rnd, g.build_indexes_cdef(torch.from_numpy(rnd)).numpy().astype(np.int16)),
+            ("nan", np.full(64, np.nan, np.float32), np.zeros(64, np.int16))]
+    for name, x, want in sets:
+        n = x.size + (-x.size) % 32                           # whole rows of 16 (MV channels) x 2 (parity classes)
+        s = np.concatenate([x, np.full(n - x.size, x[0], np.float32)])
+        want = np.concatenate([want, np.full(n - x.size, want[0], np.int16)])
+        sd = torch.from_numpy(s).cuda()
+        # four-step sites: one plane of 2 x n/2, the four parity classes together cover every position
+        H, W = 2, n // 2
+        params = torch.stack([sd, torch.zeros_like(sd)], -1).view(1, H, W, 2).contiguous()
+        x4 = torch.zeros(1, 1, H, W, device="cuda")
+        got_i = torch.zeros(n, dtype=torch.int16, device="cuda")
+        got_q = torch.zeros(n, dtype=torch.int16, device="cuda")
+        for k in range(4):
+            got_i += ops.fourstep_indexes(params, 1, H, W, k, lmin, lstep)
+            sym = torch.zeros(n, dtype=torch.int16, device="cuda")
+            idx = torch.zeros(n, dtype=torch.int16, device="cuda")
+            ops.fourstep_quant(x4, params, torch.zeros_like(x4), sym, idx, 0, k, lmin, lstep)
+            got_q += idx
+        assert_same(got_i.cpu().numpy(), want, f"fourstep_indexes, {name}")
+        assert_same(got_q.cpu().numpy(), want, f"fourstep_quant, {name}")
+        sym = torch.zeros(n, dtype=torch.int16, device="cuda")
+        idx = torch.zeros(n, dtype=torch.int16, device="cuda")
+        ops.ll_quant(x4, params, sym, idx, 0, lmin, lstep)
+        assert_same(idx.cpu().numpy(), want, f"ll_quant, {name}")
+        # MV four-part sites: HW positions x 16 channels, scale of (p, cc) in all four channel groups; rows [16][HW]
+        HW = n // 16
+        sc = sd.view(HW, 1, 16).expand(HW, 4, 16).reshape(HW, 64)
+        common = torch.cat([torch.ones(HW, 64, device="cuda"), sc, torch.zeros(HW, 64, device="cuda")], 1).contiguous()
+        sp = torch.cat([sc, torch.zeros(HW, 64, device="cuda")], 1).contiguous()
+        want_mv = want.reshape(HW, 16).T.reshape(-1)
+        for t in range(4):
+            got = ops.mv_fourpart_indexes(common, sp, 1, HW, t, lmin, lstep)
+            assert_same(got.cpu().numpy(), want_mv, f"mv_fourpart_indexes t={t}, {name}")
+        for t in range(4):
+            y = torch.zeros(1, 1, HW, 64, device="cuda")
+            sym = torch.zeros(16 * HW, dtype=torch.int16, device="cuda")
+            idx = torch.zeros(16 * HW, dtype=torch.int16, device="cuda")
+            ops.mv_fourpart_step(y, common, sp, torch.zeros(1, 1, HW, 64, device="cuda"), sym, idx, 0, t, lmin, lstep)
+            assert_same(idx.cpu().numpy(), want_mv, f"mv_fourpart t={t}, {name}")

@@ -37,6 +37,22 @@ def test_build_indexes_kat_both_backends():
     assert g.build_indexes_cdef(sc).tolist() == INDEXES
 
 
+def test_build_indexes_cdef_at_every_row_boundary():
+    """PM-F32's row selection against the reference formula's rows (tools/make_scale_index_fixture.py) at +-64 ulps of
+    every one of the 255 row boundaries, at the 1e-5 floor, at scale_max, and on 0, -0, negatives, denormals and +-inf."""
+    from helpers import golden
+    from pmctf_oracle import entropy
+    g = entropy.GaussianTables()
+    d = golden("reference_scale_index_boundaries.npz")
+    x, rows = d["scale_x"], d["scale_row"].astype(np.int32)
+    assert not np.isnan(x).any() and x.size > 255 * 129
+    # the fixture does straddle every boundary: both neighbouring rows of every k occur
+    assert set(range(256)) <= set(rows.tolist())
+    got = g.build_indexes_cdef(torch.from_numpy(x)).numpy()
+    bad = np.nonzero(got != rows)[0]
+    assert bad.size == 0, f"{bad.size} rows differ, first scale {x[bad[0]]!r}: {got[bad[0]]} vs reference {rows[bad[0]]}"
+
+
 def test_rans_known_answer_stream_and_roundtrip():
     from pmctf_oracle import entropy
     g = entropy.GaussianTables()

@@ -617,3 +617,57 @@ def test_bench_dump_outputs_types_budget_and_sample(monkeypatch):
         flat = y.numpy().reshape(-1)
         assert np.isin(a["frame00_y.npy"], flat).all() and len(np.unique(a["frame00_y.npy"])) == 1000
         assert all(np.array_equal(a[n], b[n]) for n in a)
+
+
+@pytest.mark.parametrize("case", [((1, 3, 7), (1, 48, 16), "s0"), ((2, 2, 5), (0, 80, 0), "m-"),
+                                  ((1, 2, 4), (0, 0, 112), "lo")])
+def test_ll_sequential_decode_equals_the_one_shot_network_under_forced_rules(case):
+    """The premise of tests/test_gpu_ll_decode.py: under a forced rule triple, the oracle's position-by-position LL decode
+    (Oracle.ll_sequential_decode) of the stream gives the one-shot network's ll_hat, and leaves the stream where the host
+    decoder says the LL ends."""
+    import ll_decode_helper as hp
+    from pmctf_oracle import entropy
+    (N, H, W), rules, ws = case
+    orc = hp.weight_sets([ws])[ws]
+    tabs = tuple(np.ascontiguousarray(a, dtype=np.int32) for a in orc.tables.cdf_info())
+    lead, trail = hp.side_symbols(1, 11, tabs), hp.side_symbols(2, 16, tabs)
+    c = hp.make_case(orc, rules, hp.ll_for(hp.ll_planes(), N, H, W, 5), lead, trail)
+    o = hp.Oracle_with_rules(orc, rules)
+    o.ec = entropy.EntropyCoder()
+    o.ec.set_stream(c["stream"])
+    assert o.ec.decode_stream(torch.from_numpy(lead[1]), *tabs).int().numpy().tolist() == lead[0].tolist()
+    rec = o.ll_sequential_decode(hp.CODER, N, H, W)
+    assert torch.equal(rec[:, 0], torch.from_numpy(c["ll_hat"]))
+    assert o.ec.decode_stream(torch.from_numpy(trail[1]), *tabs).int().numpy().tolist() == trail[0].tolist()
+
+
+def test_ll_kernel_choice_mirror_tracks_the_source():
+    """tests/ll_decode_helper.py restates how pmctf_ll_ar_decode_rules_f32 picks a kernel (lds_bytes, kernel_for) to
+    label and count what tests/test_gpu_ll_decode.py exercised.  Read the LDS estimate, its constants and the branch
+    conditions from decode_ops.hip and hold the restatement to them, so that the two cannot drift apart."""
+    import re
+    import ll_decode_helper as hp
+    src = open(os.path.join(ROOT, "learned-pmctf_amd", "csrc", "decode_ops.hip")).read()
+    const = {n: int(re.search(rf"constexpr int {n} = (\d+);", src).group(1)) for n in ("NF", "TB")}
+    assert const["NF"] == hp.NF
+    body = src[src.index('extern "C" int pmctf_ll_ar_decode_rules_f32'):]
+    body = body[:body.index("\n}\n")]
+    flat = " ".join(body.split())
+    smem = re.search(r"const size_t smem = (.*?);", flat).group(1)
+    smem2 = re.search(r"const size_t smem2 = smem \+ (.*?);", flat).group(1)
+    c_expr = lambda e: e.replace("(size_t)", "").replace("sizeof(int32_t)", "4").replace("sizeof(float)", "4")
+    for N in (1, 2, 3, 4):
+        for W in (1, 7, 88, 89, 344, 345, 2676, 2677, 2932, 2933):
+            env = dict(const, N=N, W=W, cdf_cols=103)
+            s = eval(c_expr(smem), {}, env)
+            assert hp.lds_bytes(N, W, 103) == (s, s + eval(c_expr(smem2), {}, env)), (N, W)
+    # the branches kernel_for restates, in this order
+    conds = ["if (!v1 && !v2 && a.blocks && N <= 2 && smem <= 150 * 1024)", "if (one_thread || smem2 > 150 * 1024)",
+             "if (!v1 && N <= 2 && smem <= 150 * 1024)"]
+    at = [flat.find(c) for c in conds]
+    assert all(a >= 0 for a in at) and at == sorted(at), at
+    for name, switch in (("v1", "PMCTF_LL_AR_V1"), ("v2", "PMCTF_LL_AR_V2"), ("one_thread", "PMCTF_LL_AR_ROW1")):
+        assert f'static const bool {name} = getenv("{switch}") != nullptr;' in flat
+    assert "if (N == 1) row(ll_ar_pre_kernel<1>, ll_ar_row_kernel<1>" in flat
+    assert "if (N == 1) row(ll_ar_pre_kernel<1>, ll_ar_row2_kernel<1>" in flat
+    assert "PM_LAUNCH(ll_ar_decode_kernel" in flat
