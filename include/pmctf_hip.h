@@ -329,6 +329,38 @@ int pmctf_ll_ar_decode_rules_f32(const float *w_packed, const uint32_t *stream_w
                                  int cdf_cols, float log_scale_min, float log_scale_step, float *ll_out,
                                  float *scratch_zeroed, int N, int H, int W, uint64_t *state_out, int sum_rule_3x3,
                                  int sum_rule_head, int sum_rule_head_out, void *stream);
+/* Batched row-wise decode: n_jobs independent streams of the SAME geometry (P planes of H x W) in one series of launches,
+ * one workgroup per job — per row ONE launch pair for all jobs (2*H launches per batch and plane pass instead of 2*H per
+ * stream).  The job table lives in DEVICE memory; the tables, cdf_cols and the scale grid are common to the batch.
+ *   state: [0] = Rans64 state, [1] = next word index, [2] = error flag — read on entry AND written on exit, so a job
+ *   starts wherever its host decoder stands; a job whose stream runs out sets its own flag, the others are unaffected.
+ *   scratch: pmctf_ll_ar_scratch_floats(P, H, W) floats.  sum_rule_3x3 must be PMCTF_SUM_BLOCKS (the row-wise form).
+ * plane_order: PMCTF_LL_ORDER_POSITION — the P planes' symbols alternate per position (pWave.compress with
+ *   ar_order = True, what pmctf_ll_ar_decode_rules_f32 reads); PMCTF_LL_ORDER_PLANE — all of plane 0, then all of plane 1
+ *   (the one-shot order of ar_order = False): the planes are decoded one after the other as single-plane problems, each
+ *   continuing from the coder state the previous one left in `state`.  P = 1: the same launches either way.
+ * pmctf_ll_ar_batch_form: 0 = the batched form does not cover the geometry (P > 2, or planes too wide for LDS: decode such
+ *   streams one by one with pmctf_ll_ar_decode_rules_f32), 1 = one thread per channel, 2 = the two-half row kernel.
+ *   decode_batch returns PMCTF_EINVAL where batch_form is 0 or n_jobs > PMCTF_LL_BATCH_MAX_JOBS. */
+#define PMCTF_LL_ORDER_POSITION 0
+#define PMCTF_LL_ORDER_PLANE 1
+#define PMCTF_LL_BATCH_MAX_JOBS 32
+typedef struct pmctf_ll_job {
+    const float *w_packed;              /* the job's coder: pmctf_ll_ar_pack_weights() output on the device */
+    const uint32_t *stream_words;       /* rANS payload words on the device */
+    int64_t n_words;
+    uint64_t *state;                    /* [3], device */
+    float *ll_out;                      /* [P][H][W] */
+    float *scratch;
+    int32_t sum_rule_3x3, sum_rule_head, sum_rule_head_out, reserved;
+} pmctf_ll_job;                         /* 64 bytes */
+int pmctf_ll_ar_batch_form(int P, int W, int cdf_cols, int plane_order);
+int pmctf_ll_ar_decode_batch_f32(const pmctf_ll_job *jobs_dev, int n_jobs, const int32_t *cdf, const int32_t *sizes,
+                                 const int32_t *offsets, int cdf_cols, float log_scale_min, float log_scale_step, int P,
+                                 int H, int W, int plane_order, void *stream);
+/* Decoder output stage: padded float planes (N,1,Hp,Wp) -> cropped 8-bit planes (N,h,w), rint(clamp(x, 0, 255)) with ties
+ * to even (torch.round), NaN -> 0.  h <= Hp, w <= Wp. */
+int pmctf_planes_to_u8(const float *x, uint8_t *out, int N, int Hp, int Wp, int h, int w, void *stream);
 /* ContextFusionFourStep.decompress (context_fusion_4step.py:196-249): CDF rows handed to decode_stream for step k
  * (0 off the mask), then x_hat = (q + mean) on the mask.  params as in pmctf_fourstep_quant_f32. */
 int pmctf_fourstep_indexes_f32(const float *params, int16_t *idx, int N, int H, int W, int k, int params_sub,

@@ -50,6 +50,7 @@ struct LLArgs {
     float *bufs;                  // 5 activation buffers [N][(H+1)][(W+2)][NF], zero-initialised by the caller
     int N, H, W;
     unsigned long long *state_out;  // [0] = x, [1] = word position, [2] = error flag
+    int dev_state;                // row-wise form: 1 = the entry state is read from state_out as well (x0 / pos0 unused)
     // summation rules (include/pmctf_hip.h PMCTF_SUM_*), the same the encoder's one-shot network runs under:
     int blocks;                   // masked 3x3 layers: 0 = one chain from the bias, 1 = per-16-channel-block sums ("blocks")
     unsigned head_mask[3];        // 1x1 head layers convs.0/1/2: bit cb set = a reduction block ("reduce-B") ends before
@@ -59,7 +60,7 @@ struct LLArgs {
 __host__ __device__ inline long ll_scratch_acts_dev(int N, int H, int W) { return (long)5 * N * (H + 1) * (W + 2) * NF; }
 
 // reduce-B over 128 input channels: which 16-channel chunks start a new block
-inline unsigned reduce_mask(int B) {
+__host__ __device__ inline unsigned reduce_mask(int B) {
     unsigned m = 0;
     if (B >= 16 && B < NF)
         for (int cb = 1; cb < NF / 16; ++cb)
@@ -615,7 +616,7 @@ __global__ __launch_bounds__(NF) void ll_ar_stream_kernel(LLArgs a) {
 // bits, 2.25x fewer weights to stream per position (0.79 instead of 1.7 MB) and chains of 256 instead of 640 terms.
 // One launch pair per row; the coder state travels in state_out.
 template <int NP>
-__global__ __launch_bounds__(NF) void ll_ar_pre_kernel(LLArgs a, int h) {
+__device__ __forceinline__ void ll_ar_pre_body(const LLArgs &a, const int h) {
     __shared__ float act[10][NF];
     const int tid = threadIdx.x;
     const int l = blockIdx.y / NP, p = blockIdx.y % NP, w0 = blockIdx.x * 8;
@@ -649,14 +650,16 @@ __global__ __launch_bounds__(NF) void ll_ar_pre_kernel(LLArgs a, int h) {
 }
 
 template <int NP>
-__global__ __launch_bounds__(NF) void ll_ar_row_kernel(LLArgs a, int h) {
+__global__ __launch_bounds__(NF) void ll_ar_pre_kernel(LLArgs a, int h) { ll_ar_pre_body<NP>(a, h); }
+
+template <int NP>
+__device__ __forceinline__ void ll_ar_row_body(const LLArgs &a, const int h, float *smem) {
     constexpr int BLK = 4;                                // float4 groups per ring block; 40 groups (80 KB) in flight
     constexpr int RING = 10;
     constexpr int BLOCKS_R = GROUPS_R / BLK;              // 8 or 16 blocks per type-B layer
     constexpr int BLOCKS_D = GROUPS_DP / BLK;             // 5 or 10 (the last fifth is padding that is never read)
     constexpr int BLOCKS_TOTAL = 5 * BLOCKS_R + 2 * BLOCKS_D;   // 50 or 100 per position
     static_assert(BLOCKS_TOTAL % RING == 0, "a position must start at ring slot 0");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;                          // = output channel
     const int W = a.W, H = a.H;
     int32_t *l_cdf = (int32_t *)smem;                     // [256][cols]
@@ -697,9 +700,10 @@ __global__ __launch_bounds__(NF) void ll_ar_row_kernel(LLArgs a, int h) {
     };
 #pragma unroll
     for (int b = 0; b < RING - 1; ++b) request(b);
-    unsigned long long x = h == 0 ? a.x0 : a.state_out[0];
-    long pos = h == 0 ? a.pos0 : (long)a.state_out[1];
-    int err = h == 0 ? 0 : (int)a.state_out[2];
+    const bool entry = h == 0 && !a.dev_state;            // the first row of a by-value call: x0 / pos0, no error yet
+    unsigned long long x = entry ? a.x0 : a.state_out[0];
+    long pos = entry ? a.pos0 : (long)a.state_out[1];
+    int err = entry ? 0 : (int)a.state_out[2];
     // the next word of the stream is fetched when its predecessor is consumed, a position or more before it is needed
     uint32_t nw = pos < a.n_words ? a.stream[pos] : 0u;
     const float *row_prev = l_rows, *row_cur_c = l_rows + (W + 2);
@@ -937,6 +941,12 @@ __global__ __launch_bounds__(NF) void ll_ar_row_kernel(LLArgs a, int h) {
     }
 }
 
+template <int NP>
+__global__ __launch_bounds__(NF) void ll_ar_row_kernel(LLArgs a, int h) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    ll_ar_row_body<NP>(a, h, smem);
+}
+
 
 // The same row kernel on 256 threads: under rule "blocks" the eight chunk sums of an output channel are independent chains,
 // so TWO threads share a channel — chunks 0-3 and 4-7 — each streaming half of the layer's weights through its own register
@@ -995,9 +1005,10 @@ __device__ __forceinline__ void ll_ar_row2_body(const LLArgs &a, const int h, fl
     };
 #pragma unroll
     for (int b = 0; b < RING - 1; ++b) request(b);
-    unsigned long long x = h == 0 ? a.x0 : a.state_out[0];
-    long pos = h == 0 ? a.pos0 : (long)a.state_out[1];
-    int err = h == 0 ? 0 : (int)a.state_out[2];
+    const bool entry = h == 0 && !a.dev_state;            // the first row of a by-value call: x0 / pos0, no error yet
+    unsigned long long x = entry ? a.x0 : a.state_out[0];
+    long pos = entry ? a.pos0 : (long)a.state_out[1];
+    int err = entry ? 0 : (int)a.state_out[2];
     uint32_t nw = pos < a.n_words ? a.stream[pos] : 0u;
     const float *row_prev = l_rows;
     float *row_cur = l_rows + (W + 2);
@@ -1254,6 +1265,62 @@ __global__ __launch_bounds__(2 * NF) void ll_ar_row2_kernel(LLArgs a, int h) {
     else ll_ar_row2_body<NP, 1>(a, h, smem);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched row-wise decode (pmctf_ll_ar_decode_batch_f32): J independent streams of one geometry, workgroup j = job j.  The
+// kernels above take their LLArgs by value; here every workgroup builds its own from its row of the job table (device
+// memory) and the arguments common to the batch, then runs the SAME bodies — same fmaf sequences, same barriers (all of
+// them uniform per workgroup: a job whose stream ran out raises its flag and keeps arriving at them).  The entry state is
+// read from the job's state triple (dev_state), so a job starts wherever its host decoder stands, and in plane order the
+// second plane continues from what the first one left there.
+struct LLBatch {
+    const pmctf_ll_job *jobs;
+    const int32_t *cdf, *sizes, *offsets;
+    int cols;
+    float lmin, lstep;
+    int NP, H, W;                 // NP: planes the kernels decode together (position order: P; plane order: 1)
+    int plane;                    // plane order: the plane of this pass (ll_out and scratch are offset to it); else 0
+};
+
+__device__ __forceinline__ LLArgs ll_job_args(const LLBatch &b, const int j) {
+    const pmctf_ll_job &jb = b.jobs[j];
+    LLArgs a;
+    a.w = jb.w_packed; a.stream = jb.stream_words; a.n_words = jb.n_words; a.x0 = 0; a.pos0 = 0;
+    a.cdf = b.cdf; a.sizes = b.sizes; a.offsets = b.offsets; a.cols = b.cols; a.lmin = b.lmin; a.lstep = b.lstep;
+    a.N = b.NP; a.H = b.H; a.W = b.W;
+    a.ll_out = jb.ll_out + (long)b.plane * b.H * b.W;
+    a.bufs = jb.scratch + (long)b.plane * (ll_scratch_acts_dev(1, b.H, b.W) + (long)5 * b.W * 8 * NF);
+    a.state_out = (unsigned long long *)jb.state;
+    a.dev_state = 1;
+    a.blocks = 1;
+    a.head_b[0] = a.head_b[1] = jb.sum_rule_head;
+    a.head_b[2] = jb.sum_rule_head_out;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a.head_mask[i] = reduce_mask(a.head_b[i]);
+    return a;
+}
+
+template <int NP>
+__global__ __launch_bounds__(NF) void ll_ar_pre_batch_kernel(LLBatch b, int h) {
+    const LLArgs a = ll_job_args(b, blockIdx.z);
+    ll_ar_pre_body<NP>(a, h);
+}
+
+template <int NP>
+__global__ __launch_bounds__(NF) void ll_ar_row_batch_kernel(LLBatch b, int h) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const LLArgs a = ll_job_args(b, blockIdx.x);
+    ll_ar_row_body<NP>(a, h, smem);
+}
+
+// the two halves as in ll_ar_row2_kernel: one uniform branch per wave, the same barriers in both bodies
+template <int NP>
+__global__ __launch_bounds__(2 * NF) void ll_ar_row2_batch_kernel(LLBatch b, int h) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const LLArgs a = ll_job_args(b, blockIdx.x);
+    if (threadIdx.x < NF) ll_ar_row2_body<NP, 0>(a, h, smem);
+    else ll_ar_row2_body<NP, 1>(a, h, smem);
+}
+
 // four-step decompress: CDF rows of step k (0 off the mask), then x_hat at the mask positions
 __device__ __forceinline__ int scale_index(float s, float lmin, float step) {
     s = s >= 1e-5f ? s : 1e-5f;    // max(s, 1e-5); also maps NaN (corrupt stream) to row 0: pm::logf_(NaN) is finite
@@ -1460,6 +1527,7 @@ extern "C" int pmctf_ll_ar_decode_rules_f32(const float *w_packed, const uint32_
     a.lmin = log_scale_min; a.lstep = log_scale_step;
     a.ll_out = ll_out; a.bufs = scratch_zeroed; a.N = N; a.H = H; a.W = W;
     a.state_out = (unsigned long long *)state_out;
+    a.dev_state = 0;
     a.blocks = sum_rule_3x3 == PMCTF_SUM_BLOCKS;
     a.head_b[0] = a.head_b[1] = sum_rule_head;
     a.head_b[2] = sum_rule_head_out;
@@ -1506,6 +1574,60 @@ extern "C" int pmctf_ll_ar_decode_rules_f32(const float *w_packed, const uint32_
         return launch_ok();
     }
     PM_LAUNCH(ll_ar_decode_kernel, dim3(1), dim3(128 * N), 0, (hipStream_t)stream, a);
+    return launch_ok();
+}
+
+// ---- batched row-wise decode.  The LDS estimate is the one of pmctf_ll_ar_decode_rules_f32 for the planes a kernel decodes
+// together; the environment switches of that entry (A/B measurements) do not reach this one.
+constexpr int LL_BATCH_MAX_PLANES = 2;
+constexpr int LL_BATCH_LDS_LIMIT = 150 * 1024;
+inline size_t ll_batch_lds(int N, int W, int cdf_cols, bool two_half) {
+    const size_t lds = ((size_t)256 * cdf_cols + 512) * sizeof(int32_t) + ((size_t)2 * N * TB * NF + 5 * N * NF + 5 * N * 4 * NF + 7 * NF + 2 * NF + 2 + 2 * N + (size_t)N * 2 * (W + 2)) * sizeof(float) + 64;
+    return two_half ? lds + (size_t)N * 4 * NF * sizeof(float) : lds;
+}
+
+extern "C" int pmctf_ll_ar_batch_form(int P, int W, int cdf_cols, int plane_order) {
+    if (P < 1 || P > LL_BATCH_MAX_PLANES || W < 1 || cdf_cols < 3) return 0;
+    if (plane_order != PMCTF_LL_ORDER_POSITION && plane_order != PMCTF_LL_ORDER_PLANE) return 0;
+    const int N = plane_order == PMCTF_LL_ORDER_PLANE ? 1 : P;
+    if (ll_batch_lds(N, W, cdf_cols, false) > LL_BATCH_LDS_LIMIT) return 0;
+    return ll_batch_lds(N, W, cdf_cols, true) > LL_BATCH_LDS_LIMIT ? 1 : 2;
+}
+
+extern "C" int pmctf_ll_ar_decode_batch_f32(const pmctf_ll_job *jobs_dev, int n_jobs, const int32_t *cdf,
+                                            const int32_t *sizes, const int32_t *offsets, int cdf_cols, float log_scale_min,
+                                            float log_scale_step, int P, int H, int W, int plane_order, void *stream) {
+    static_assert(sizeof(pmctf_ll_job) == 64, "the job table's layout is part of the C ABI");
+    if (!jobs_dev || !cdf || !sizes || !offsets || n_jobs < 1 || n_jobs > PMCTF_LL_BATCH_MAX_JOBS || H < 1) return PMCTF_EINVAL;
+    const int form = pmctf_ll_ar_batch_form(P, W, cdf_cols, plane_order);
+    if (form == 0) return PMCTF_EINVAL;
+    LLBatch b;
+    b.jobs = jobs_dev; b.cdf = cdf; b.sizes = sizes; b.offsets = offsets; b.cols = cdf_cols;
+    b.lmin = log_scale_min; b.lstep = log_scale_step; b.H = H; b.W = W;
+    b.NP = plane_order == PMCTF_LL_ORDER_PLANE ? 1 : P;
+    const size_t lds = ll_batch_lds(b.NP, W, cdf_cols, form == 2);
+    static std::once_flag once_b[4];
+    hipStream_t st = (hipStream_t)stream;
+    auto rows = [&](auto pre_k, auto row_k, std::once_flag &flag, int threads) {
+        std::call_once(flag, [row_k] {
+            (void)hipFuncSetAttribute((const void *)row_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+        // plane order: for p in planes: for h in rows, the <1> kernels offset to plane p; position order: one pass
+        for (int p = 0; p < (b.NP == P ? 1 : P); ++p) {
+            b.plane = p;
+            for (int h = 0; h < H; ++h) {
+                if (h > 0) PM_LAUNCH(pre_k, dim3((W + 7) / 8, 5 * b.NP, n_jobs), dim3(NF), 0, st, b, h);
+                PM_LAUNCH(row_k, dim3(n_jobs), dim3(threads), lds, st, b, h);
+            }
+        }
+    };
+    if (form == 1) {
+        if (b.NP == 1) rows(ll_ar_pre_batch_kernel<1>, ll_ar_row_batch_kernel<1>, once_b[0], NF);
+        else rows(ll_ar_pre_batch_kernel<2>, ll_ar_row_batch_kernel<2>, once_b[1], NF);
+    } else {
+        if (b.NP == 1) rows(ll_ar_pre_batch_kernel<1>, ll_ar_row2_batch_kernel<1>, once_b[2], 2 * NF);
+        else rows(ll_ar_pre_batch_kernel<2>, ll_ar_row2_batch_kernel<2>, once_b[3], 2 * NF);
+    }
     return launch_ok();
 }
 

@@ -259,6 +259,7 @@ class HipEngine:
             if k.endswith(".mask"):
                 sd[k[:-5] + ".weight"] = sd[k[:-5] + ".weight"] * sd[k]
         self.sd = sd
+        self._cache_lock = threading.Lock()     # creation of the cached device objects below (conv, dwconv, lin_tables)
         self._convs = {}
         self._dw = {}
         self._lin = {}
@@ -290,6 +291,12 @@ class HipEngine:
         # configuration on: luma and chroma coders on two streams, no per-launch host work
         self.use_graphs = os.environ.get("PMCTF_GRAPHS", "1") != "0"
         self._dec_pool = None
+        self._batch_pool = None
+        self.batch_streams = []         # one per geometry group of a batched decode (pwave_decompress_batch_begin)
+        # host threads that finish the files of a batched decode (at most 16).  Measured on a 1080p GOP 16 (32 files,
+        # tools/time_decode_gop.py): 2.93 / 2.89 / 2.98 / 3.03 s with 2 / 4 / 8 / 16 threads — the threads spend their time
+        # in Python between launches and host range decoding, so more of them only contend
+        self.decode_workers = 4
         self.pair_plans = {}
         self._plan_ctx = {}             # per host thread: graph memory pools and streams of its launch plans
         self.plan_timing = None         # a list: launch plans append (start, motion, luma, chroma, luma syn, chroma syn) events
@@ -387,28 +394,40 @@ class HipEngine:
         key = (p, stride, padding)
         c = self._convs.get(key)
         if c is None:
-            w = self.sd[p + ".weight"]
-            c = ops.Conv2d(w, self.sd.get(p + ".bias"), stride, (padding, padding), self.dev,
-                           split=self.nsplit, rule=self.sum_rule(p, w, stride))
-            torch.cuda.synchronize(self.dev)      # packed weights are used from several streams later
-            self._convs[key] = c
+            # One object per layer, ever: the host threads of a decode reach a layer for the first time together.  A second
+            # copy that replaced the first in the cache would let the first be freed while another thread's launch, on
+            # another stream, still reads its weights — and the allocator hands that memory out again at once.
+            with self._cache_lock:
+                c = self._convs.get(key)
+                if c is None:
+                    w = self.sd[p + ".weight"]
+                    c = ops.Conv2d(w, self.sd.get(p + ".bias"), stride, (padding, padding), self.dev,
+                                   split=self.nsplit, rule=self.sum_rule(p, w, stride))
+                    torch.cuda.synchronize(self.dev)      # packed weights are used from several streams later
+                    self._convs[key] = c
         return c
 
     def dwconv(self, p):
         c = self._dw.get(p)
         if c is None:
-            c = ops.DepthwiseConv2d(self.sd[p + ".weight"], self.sd.get(p + ".bias"), self.dev)
-            torch.cuda.synchronize(self.dev)
-            self._dw[p] = c
+            with self._cache_lock:
+                c = self._dw.get(p)
+                if c is None:
+                    c = ops.DepthwiseConv2d(self.sd[p + ".weight"], self.sd.get(p + ".bias"), self.dev)
+                    torch.cuda.synchronize(self.dev)
+                    self._dw[p] = c
         return c
 
     def lin_tables(self, H, W):
         """the cached linspace(-1,1,.) grids of video_net.py:33-40 (built once per shape, on the host)"""
         t = self._lin.get((H, W))
         if t is None:
-            t = (torch.linspace(-1.0, 1.0, W).to(self.dev), torch.linspace(-1.0, 1.0, H).to(self.dev))
-            torch.cuda.synchronize(self.dev)
-            self._lin[(H, W)] = t
+            with self._cache_lock:
+                t = self._lin.get((H, W))
+                if t is None:
+                    t = (torch.linspace(-1.0, 1.0, W).to(self.dev), torch.linspace(-1.0, 1.0, H).to(self.dev))
+                    torch.cuda.synchronize(self.dev)
+                    self._lin[(H, W)] = t
         return t
 
     def warp(self, im, flow, sign=1.0):
@@ -1090,6 +1109,15 @@ class HipEngine:
         """device int16 CDF rows -> host range decoder -> device int16 symbols"""
         return torch.from_numpy(dec.decode(idx_dev.cpu().numpy(), table)).to(self.dev)
 
+    def _ll_rules(self, coder, N, H, W):
+        """the rules of the encoder's one-shot network (context_fusion_ll on N planes of H x W), layer for layer"""
+        p = f"{coder}.context_fusion.{self.L - 1}.ll"
+        rules = []
+        for name in (".maskedConv2", ".convs.0", ".convs.2"):
+            r = self.sum_rule(p + name, self.sd[p + name + ".weight"])
+            rules.append(r(N, H, W) if callable(r) else r)
+        return rules
+
     def ll_ar_launch(self, coder, dec, N, H, W, stream=None):
         """Enqueue the sequential LL decode (one persistent workgroup) on `stream`; returns a ticket for ll_ar_finish.
         The LL streams of different files are independent, so callers start all of them before waiting for any."""
@@ -1106,12 +1134,7 @@ class HipEngine:
             scratch = torch.zeros(L.pmctf_ll_ar_scratch_floats(N, H, W), dtype=torch.float32, device=self.dev)
             state = torch.zeros(3, dtype=torch.int64, device=self.dev)
             vp = lambda t: C.c_void_p(t.data_ptr())
-            # the rules of the encoder's one-shot network (context_fusion_ll), layer for layer
-            p = f"{coder}.context_fusion.{self.L - 1}.ll"
-            rules = []
-            for name in (".maskedConv2", ".convs.0", ".convs.2"):
-                r = self.sum_rule(p + name, self.sd[p + name + ".weight"])
-                rules.append(r(N, H, W) if callable(r) else r)
+            rules = self._ll_rules(coder, N, H, W)
             _lib.check(L.pmctf_ll_ar_decode_rules_f32(vp(w), vp(words), words.numel(), C.c_uint64(x), pos, vp(cdf),
                                                       vp(sizes), vp(offsets), cdf.shape[1], float(self.lmin),
                                                       float(self.lstep), vp(ll), vp(scratch), N, H, W, vp(state),
@@ -1212,6 +1235,181 @@ class HipEngine:
         if self._dec_pool is None:
             self._dec_pool = ThreadPoolExecutor(max_workers=4)
         out = list(self._dec_pool.map(finish, range(len(begun))))
+        for i, t in enumerate(out):
+            main.wait_stream(self.side_streams[i])
+            t.record_stream(main)
+        return out
+
+    # ---- a whole GOP's files at once: batched LL decode (one launch pair per row and geometry), then the files' four-step
+    # parts on host threads
+    LL_ORDERS = {"position": 0, "plane": 1}          # PMCTF_LL_ORDER_* of include/pmctf_hip.h
+    LL_BATCH_MAX_JOBS = 32                           # PMCTF_LL_BATCH_MAX_JOBS
+    LL_BATCH_MAX_PLANES = 2
+    LL_BATCH_LDS_LIMIT = 150 * 1024
+    LL_JOB = np.dtype([("w", "<u8"), ("words", "<u8"), ("n_words", "<i8"), ("state", "<u8"), ("ll", "<u8"),
+                       ("scratch", "<u8"), ("rules", "<i4", (3,)), ("reserved", "<i4")])   # pmctf_ll_job, 64 bytes
+
+    @classmethod
+    def ll_batch_form(cls, P, W, cols, ll_order, rule3=ops.SUM_BLOCKS):
+        """Mirror of pmctf_ll_ar_batch_form (decode_ops.hip) plus the rule the row-wise form needs: 0 = per-file launches
+        (rule "chain", more than two planes, planes too wide for LDS), 1 = batched, one thread per channel, 2 = batched,
+        the two-half row kernel."""
+        NF, TB = 128, 5
+        if rule3 != ops.SUM_BLOCKS or not 1 <= P <= cls.LL_BATCH_MAX_PLANES or W < 1 or ll_order not in cls.LL_ORDERS:
+            return 0
+        N = 1 if ll_order == "plane" else P
+        lds = (256 * cols + 512) * 4 + (2 * N * TB * NF + 5 * N * NF + 5 * N * 4 * NF + 7 * NF + 2 * NF + 2 + 2 * N
+                                        + N * 2 * (W + 2)) * 4 + 64
+        if lds > cls.LL_BATCH_LDS_LIMIT:
+            return 0
+        return 1 if lds + N * 4 * NF * 4 > cls.LL_BATCH_LDS_LIMIT else 2
+
+    def ll_ar_launch_batch(self, items, N, H, W, ll_order, stream):
+        """items: [(coder, dec)] — streams of one geometry the batched form covers.  Uploads each stream's words once,
+        fills the job table and issues the batched launches on `stream`; returns one ll_ar_finish ticket per item."""
+        L = _lib.hip()
+        cdf, sizes, offsets = self._dev_tables("gauss")
+        n_scr = L.pmctf_ll_ar_scratch_floats(N, H, W)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        tickets = []
+        for at in range(0, len(items), self.LL_BATCH_MAX_JOBS):
+            part = items[at:at + self.LL_BATCH_MAX_JOBS]
+            J = len(part)
+            with torch.cuda.stream(stream):
+                host_state = np.zeros((J, 3), np.uint64)
+                for j, (_, dec) in enumerate(part):
+                    host_state[j, :2] = dec.get_state()
+                state = torch.from_numpy(host_state.view(np.int64)).to(self.dev)
+                ll = torch.zeros((J, N, 1, H, W), dtype=torch.float32, device=self.dev)
+                scratch = torch.zeros((J, n_scr), dtype=torch.float32, device=self.dev)
+                words = [torch.from_numpy(dec.words.copy() if dec.words.size else np.zeros(1, np.uint32)).to(self.dev)
+                         for _, dec in part]
+                table = np.zeros(J, self.LL_JOB)
+                for j, (coder, dec) in enumerate(part):
+                    rules = self._ll_rules(coder, N, H, W)
+                    if self.ll_batch_form(N, W, cdf.shape[1], ll_order, rules[0]) == 0:
+                        raise ValueError("ll_ar_launch_batch: a stream the batched form does not cover")
+                    table[j] = (self._ll_weights(coder).data_ptr(), words[j].data_ptr(), dec.words.size,
+                                state[j].data_ptr(), ll[j].data_ptr(), scratch[j].data_ptr(), rules, 0)
+                jobs_dev = torch.from_numpy(table.view(np.uint8)).to(self.dev)
+                _lib.check(L.pmctf_ll_ar_decode_batch_f32(vp(jobs_dev), J, vp(cdf), vp(sizes), vp(offsets), cdf.shape[1],
+                                                          float(self.lmin), float(self.lstep), N, H, W,
+                                                          self.LL_ORDERS[ll_order], C.c_void_p(stream.cuda_stream)),
+                           "ll_ar_decode_batch")
+            for j, (_, dec) in enumerate(part):
+                tickets.append({"dec": dec, "ll": ll[j], "state": state[j], "stream": stream,
+                                "keep": (words[j], scratch, jobs_dev, ll, state), "path": "batched"})
+        return tickets
+
+    def _ll_ar_planes_one_by_one(self, coder, dec, N, H, W, stream):
+        """plane order outside the batched form: one single-plane call after the other, the state read back in between"""
+        rules = self._ll_rules(coder, N, H, W)
+        L = _lib.hip()
+        w = self._ll_weights(coder)
+        cdf, sizes, offsets = self._dev_tables("gauss")
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.stream(stream):
+            words = torch.from_numpy(dec.words.copy()).to(self.dev)
+            ll = torch.zeros((N, 1, H, W), dtype=torch.float32, device=self.dev)
+            state = torch.zeros(3, dtype=torch.int64, device=self.dev)
+            keep = [words]
+            for p in range(N):
+                x, pos = dec.get_state()
+                scratch = torch.zeros(L.pmctf_ll_ar_scratch_floats(1, H, W), dtype=torch.float32, device=self.dev)
+                keep.append(scratch)
+                _lib.check(L.pmctf_ll_ar_decode_rules_f32(vp(w), vp(words), words.numel(), C.c_uint64(x), pos, vp(cdf),
+                                                          vp(sizes), vp(offsets), cdf.shape[1], float(self.lmin),
+                                                          float(self.lstep), vp(ll[p]), vp(scratch), 1, H, W, vp(state),
+                                                          rules[0], rules[1], rules[2], C.c_void_p(stream.cuda_stream)),
+                           "ll_ar_decode")
+                if p + 1 < N:
+                    self.ll_ar_finish({"dec": dec, "ll": ll, "state": state, "stream": stream})
+        return {"dec": dec, "ll": ll, "state": state, "stream": stream, "keep": keep, "path": "per-file"}
+
+    def pwave_decompress_batch_begin(self, jobs, ll_order="position"):
+        """jobs: [(coder, data, padding, q_index, qp_scale)] as for pwave_decompress_many_begin — typically every picture
+        file of a GOP.  The files are grouped by geometry; the sequential LL parts of a group the batched form covers run
+        as ONE series of launches (a workgroup per file) on the group's stream, the others as per-file launches on side
+        streams.  ll_order: "position" (files written with ar_order=True) or "plane" (the one-shot order of
+        skip_decoding=True).  Finish with pwave_decompress_batch_end."""
+        import struct
+        if ll_order not in self.LL_ORDERS:
+            raise ValueError(f"ll_order must be one of {sorted(self.LL_ORDERS)}")
+        cols = self.tables["gauss"][0].shape[1]
+        begun, groups = [], {}
+        for i, (coder, data, padding, q_index, qp_scale) in enumerate(jobs):
+            if len(data) < 16:
+                raise ValueError("bitstream file shorter than its header")
+            height, width, N = struct.unpack(">III", data[:12])
+            (n,) = struct.unpack(">I", data[12:16])
+            if not (1 <= N <= 4 and height >= 1 and width >= 1 and n >= 1 and len(data) >= 16 + n):
+                raise ValueError("bitstream file with an implausible or truncated header")
+            dec = HostDecoder(self.tables, data[16:16 + n])
+            new_h = (height + padding - 1) // padding * padding
+            new_w = (width + padding - 1) // padding * padding
+            sh, sw = new_h >> self.L, new_w >> self.L
+            form = self.ll_batch_form(N, sw, cols, ll_order, self._ll_rules(coder, N, sh, sw)[0])
+            begun.append({"coder": coder, "dec": dec, "ticket": None, "q": self.q_scales(coder, q_index, qp_scale), "N": N,
+                          "shape": (new_h, new_w, sh, sw)})
+            groups.setdefault((N, sh, sw, form), []).append(i)
+        while len(self.side_streams) < len(jobs):
+            self.side_streams.append(torch.cuda.Stream(device=self.dev))
+        while len(self.batch_streams) < len(groups):
+            self.batch_streams.append(torch.cuda.Stream(device=self.dev))
+        # the longest series first: luma's LL planes have four times the positions of chroma's
+        order = sorted(groups, key=lambda g: -(g[1] * g[2] * (g[0] if ll_order == "plane" else 1)))
+        for k, key in enumerate(order):
+            N, sh, sw, form = key
+            members = groups[key]
+            if form:
+                tickets = self.ll_ar_launch_batch([(begun[i]["coder"], begun[i]["dec"]) for i in members], N, sh, sw,
+                                                  ll_order, self.batch_streams[k])
+                for i, t in zip(members, tickets):
+                    begun[i]["ticket"] = t
+            else:
+                for i in members:
+                    b = begun[i]
+                    if ll_order == "plane" and N > 1:
+                        b["ticket"] = self._ll_ar_planes_one_by_one(b["coder"], b["dec"], N, sh, sw, self.side_streams[i])
+                    else:
+                        b["ticket"] = dict(self.ll_ar_launch(b["coder"], b["dec"], N, sh, sw, self.side_streams[i]),
+                                           path="per-file")
+        return begun
+
+    def pwave_decompress_batch_end(self, begun, names=None):
+        """The four-step parts of the begun files on host threads (self.decode_workers of them), each file on its own
+        stream, as pwave_decompress_many_end does for the files of one pair.  names: one label per file, put in front of
+        the ValueError a damaged file raises."""
+        main = torch.cuda.current_stream(self.dev)
+        ready = torch.cuda.Event()
+        ready.record(main)
+
+        def finish(i):
+            torch.cuda.set_device(self.dev)
+            st = self.side_streams[i]
+            st.wait_event(ready)
+            try:
+                with torch.no_grad(), torch.cuda.stream(st):
+                    return self.pwave_decompress_end(begun[i])
+            except (ValueError, RuntimeError) as e:
+                if names is None:
+                    raise
+                raise ValueError(f"{names[i]}: {e}") from e
+        workers = max(1, min(16, int(self.decode_workers)))
+        if self._batch_pool is None or self._batch_pool[0] != workers:
+            self._batch_pool = (workers, ThreadPoolExecutor(max_workers=workers))
+        # the files whose LL part ends first (chroma: a quarter of luma's positions) are finished first
+        first = sorted(range(len(begun)), key=lambda i: begun[i]["shape"][2] * begun[i]["shape"][3])
+        futures = {i: self._batch_pool[1].submit(finish, i) for i in first}
+        out, err = [], None
+        for i in range(len(begun)):
+            try:
+                out.append(futures[i].result())
+            except Exception as e:  # noqa: BLE001 - every thread is waited for before the first failure is reported
+                out.append(None)
+                err = err or e
+        if err is not None:
+            raise err
         for i, t in enumerate(out):
             main.wait_stream(self.side_streams[i])
             t.record_stream(main)

@@ -410,6 +410,15 @@ def ll_quant(ll, params, sym, idx, off, lmin, lstep, ar_order=False):
     return ll_hat
 
 
+def planes_to_u8(x, h, w):
+    """decoder output stage: padded planes (N,1,Hp,Wp) float32 -> cropped (N,h,w) uint8, round-half-even of clamp(x, 0, 255)"""
+    N, _, Hp, Wp = x.shape
+    out = torch.empty((N, h, w), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.hip().pmctf_planes_to_u8(_p(x), C.c_void_p(out.data_ptr()), N, Hp, Wp, int(h), int(w), _stream()),
+               "planes_to_u8")
+    return out
+
+
 def _pi16(t):
     assert t.is_cuda and t.dtype == torch.int16 and t.is_contiguous()
     return C.c_void_p(t.data_ptr())

@@ -353,6 +353,37 @@ class pMCTF(nn.Module):
 
     @torch.no_grad()
     @_gated
+    def decompress_gop_files(self, files, psize=128, q_index=0, ll_order="position"):
+        """Picture files of any number of pairs and stages in one call.  files: [(data, ischroma, low, stage_idx)] — the
+        bytes of one file, whether it holds the two chroma planes, whether it is an L file (lp_coder) or an H file
+        (hp_coder, de-quantised with stage_idx's scale).  Returns the x_hat planes in the order of `files`.
+        ll_order: see HipEngine.pwave_decompress_batch_begin."""
+        return self._decompress_gop_files_end(self._decompress_gop_files_begin(files, psize, q_index, ll_order))
+
+    @torch.no_grad()
+    @_gated
+    def _decompress_gop_files_begin(self, files, psize, q_index, ll_order, names=None):
+        """start the sequential LL decodes of all files (batched per geometry); finish with _decompress_gop_files_end"""
+        from pMCTF.hip.engine import get_curr_q
+        self.flush()
+        eng = self.engine()
+        jobs = []
+        for data, ischroma, low, stage_idx in files:
+            pad = psize // 2 if ischroma else psize
+            qp_scale = None
+            if not low and self.quant_stage:
+                qp_scale = get_curr_q(eng.sd[f"hp_q_scale.{stage_idx}"], q_index)
+            jobs.append(("lp_coder" if low else "hp_coder", data, pad, q_index, qp_scale))
+        return eng.pwave_decompress_batch_begin(jobs, ll_order), names
+
+    @torch.no_grad()
+    @_gated
+    def _decompress_gop_files_end(self, begun):
+        jobs, names = begun
+        return self.engine().pwave_decompress_batch_end(jobs, names)
+
+    @torch.no_grad()
+    @_gated
     def encode_stage_pairs(self, pairs, code_lt, dpb, output_paths, pic_width, pic_height, psize=128, stage_idx=0,
                            q_index=0, chain_reset=(), me_downsample=1, wait_files=True):
         """All pairs of one temporal stage in one call: pairs = [(ref_frame, cur_frame)], output_paths = ["k.bin"].

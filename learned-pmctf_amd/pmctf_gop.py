@@ -250,12 +250,14 @@ def rgb_psnr(rec_y, rec_c, y, c):
 
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                    skip_decoding=True, psize=128):
+                    skip_decoding=True, psize=128, keep_gops=False):
     """What the evaluation harness produces for one sequence (test_pMCTF_flex.py:run_test, 86-346) built from this
     module's own pieces: pictures come from a planar .yuv through YUVReader and get_padding_size, every closed GOP goes
     through encode_gop (one encode_one_stage call per pair, both per-pair report lines), decode_gop and gop_psnr, and
     the per-frame tables are folded into the harness's log record by generate_log_json / dump_json.  MS-SSIM is
     reported as 0 (pytorch_msssim is a third-party package the harness imports; not part of the path).
+    keep_gops=True: GOP k goes to bin_folder/gop_{k:05d}/ instead of overwriting GOP k-1's files, and bin_folder gets the
+    sequence.json header decode_sequence needs (write_sequence_header).
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"}."""
     import io
     import time
@@ -269,9 +271,13 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
     t0 = time.time()
     with torch.no_grad():
-        for _ in range(frame_num // gop):
+        for k in range(frame_num // gop):
             padded, orig, (h, w) = read_gop(reader, gop, device, psize)
-            enc = encode_gop(codec, padded, h, w, q_index, bin_folder, skip_decoding=skip_decoding, psize=psize)
+            folder = bin_folder
+            if keep_gops:
+                folder = os.path.join(bin_folder, gop_folder(k))
+                os.makedirs(folder, exist_ok=True)
+            enc = encode_gop(codec, padded, h, w, q_index, folder, skip_decoding=skip_decoding, psize=psize)
             for r in enc["results"]:
                 pairs += 1
                 for k in seconds:
@@ -288,6 +294,10 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                 crop_c = torch.round(rc.clamp(0, 255.0))[:, :, :h // 2, :w // 2]
                 tables["psnr_rgb"].append(rgb_psnr(crop_y, crop_c, y, c))
     reader.close()
+    if keep_gops:
+        write_sequence_header(bin_folder, width=width, height=height, frame_num=frame_num, gop=gop, q_index=q_index,
+                              psize=psize, me_downsample=1, ll_order="plane" if skip_decoding else "position",
+                              **codec_header_fields(codec))
     for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
         lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
     record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
@@ -295,3 +305,217 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     text = io.StringIO()
     dump_json(record, text, float_digits=6, indent=2)
     return dict(tables, log=record, json=text.getvalue(), lines=lines)
+
+
+# ---------------------------------------------------------------------------------------------------- decoding from files
+SEQUENCE_HEADER = "sequence.json"
+SEQUENCE_FORMAT_VERSION = 1
+SEQUENCE_FIELDS = ("width", "height", "frame_num", "gop", "q_index", "psize", "me_downsample", "num_me_stages", "ll_order",
+                   "precision", "aten_threads")
+LL_ORDERS = ("position", "plane")
+
+
+def gop_folder(k):
+    """sub-folder of GOP k in a sequence written with encode_sequence(keep_gops=True)"""
+    return f"gop_{k:05d}"
+
+
+def gop_pairs(gop):
+    """[(stage, i_ref, i_cur)] in coding order: stage s codes the pairs (2k*2^s, 2k*2^s + 2^s)"""
+    stages = int(round(math.log2(gop)))
+    if 2 ** stages != gop or gop < 2:
+        raise ValueError("the GOP length must be a power of two, at least 2")
+    return [(s, g * 2 * 2 ** s, g * 2 * 2 ** s + 2 ** s) for s in range(stages) for g in range(gop >> (s + 1))]
+
+
+def gop_file_names(gop):
+    """the files encode_gop writes for one GOP, in coding order: per pair the H picture's luma, chroma and motion files;
+    the one L picture's luma and chroma files come with the last pair"""
+    names = []
+    for _, _, i_cur in gop_pairs(gop):
+        names += [f"{i_cur}.bin", f"{i_cur}_C_main.bin", f"{i_cur}_mv.bin"]
+    return names + ["0_main.bin", "0_C_main.bin"]
+
+
+def codec_header_fields(codec):
+    """what a decoder must share with the encoder beyond the weights: the number of motion stages, the engine's
+    arithmetic profile and the thread count its torch.sigmoid restatement assumes (PMCTF_ATEN_THREADS as the engine
+    read it)"""
+    eng = codec.engine()
+    return {"num_me_stages": int(codec.num_me_stages), "precision": str(eng.precision),
+            "aten_threads": int(eng.aten_threads)}
+
+
+def write_sequence_header(bin_folder, **fields):
+    """bin_folder/sequence.json: format version + SEQUENCE_FIELDS (all required, nothing else accepted)"""
+    import json
+    if set(fields) != set(SEQUENCE_FIELDS):
+        raise ValueError(f"sequence header fields: missing {sorted(set(SEQUENCE_FIELDS) - set(fields))}, "
+                         f"unknown {sorted(set(fields) - set(SEQUENCE_FIELDS))}")
+    if fields["ll_order"] not in LL_ORDERS:
+        raise ValueError(f"ll_order must be one of {LL_ORDERS}")
+    record = {"format_version": SEQUENCE_FORMAT_VERSION}
+    record.update({k: fields[k] if k in ("ll_order", "precision") else int(fields[k]) for k in SEQUENCE_FIELDS})
+    path = os.path.join(bin_folder, SEQUENCE_HEADER)
+    with open(path, "w") as f:
+        json.dump(record, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return path
+
+
+def read_sequence_header(bin_folder):
+    import json
+    path = os.path.join(bin_folder, SEQUENCE_HEADER)
+    try:
+        with open(path) as f:
+            record = json.load(f)
+    except FileNotFoundError:
+        raise ValueError(f"{path}: missing (not a folder written with encode_sequence(keep_gops=True))") from None
+    except json.JSONDecodeError as e:
+        raise ValueError(f"{path}: not a sequence header ({e})") from None
+    if not isinstance(record, dict) or record.get("format_version") != SEQUENCE_FORMAT_VERSION:
+        got = record.get("format_version") if isinstance(record, dict) else None
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {SEQUENCE_FORMAT_VERSION}")
+    missing = [k for k in SEQUENCE_FIELDS if k not in record]
+    if missing:
+        raise ValueError(f"{path}: fields {missing} missing")
+    if record["ll_order"] not in LL_ORDERS:
+        raise ValueError(f"{path}: ll_order {record['ll_order']!r}")
+    if record["frame_num"] % record["gop"]:
+        raise ValueError(f"{path}: frame_num {record['frame_num']} is not a multiple of gop {record['gop']}")
+    return record
+
+
+def check_sequence_header(header, codec_fields):
+    """refuse a decoder whose motion stages, arithmetic profile or ATen thread setting differ from the encoder's: its
+    entropy parameters would differ in their last bits and the streams desynchronise silently"""
+    diff = {k: (header[k], v) for k, v in codec_fields.items() if header[k] != v}
+    if diff:
+        raise ValueError("the sequence was coded with a different codec configuration: " +
+                         ", ".join(f"{k} {a!r} in the header, {b!r} here" for k, (a, b) in sorted(diff.items())))
+
+
+def _read_framed(path, header_bytes):
+    """the bytes of a bitstream file whose header ends with a big-endian uint32 payload length; ValueError naming the
+    file when it is missing, cut short or longer than its header says"""
+    import struct
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+    except FileNotFoundError:
+        raise ValueError(f"{path}: missing") from None
+    if len(data) < header_bytes:
+        raise ValueError(f"{path}: truncated ({len(data)} bytes, shorter than its header)")
+    (n,) = struct.unpack(">I", data[header_bytes - 4:header_bytes])
+    if len(data) < header_bytes + n:
+        raise ValueError(f"{path}: truncated ({len(data)} bytes, the header announces {header_bytes + n})")
+    if len(data) > header_bytes + n:
+        raise ValueError(f"{path}: {len(data) - header_bytes - n} surplus bytes after the announced {header_bytes + n}")
+    return data
+
+
+def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize=128, me_downsample=1, ll_order="plane",
+                     luma_stage0=False):
+    """Decode one GOP from the files encode_gop wrote into bin_folder, with nothing else from the encoder.
+    Every picture file of the GOP is started as ONE batch (their sequential LL parts side by side, batched per geometry:
+    codec._decompress_gop_files_begin); under them the motion files are decoded stage by stage, pair by pair in coding
+    order (the motion context restarts per stage, as in encode_gop; a reduced-resolution motion stream is decoded at the
+    size it was coded at); then the files' remaining subbands are finished and the temporal synthesis (decode_gop) runs.
+    ll_order: "plane" for files written with skip_decoding=True (chroma's LL symbols plane after plane), "position" for
+    decoder-order files (skip_decoding=False).
+    Returns {"frames": [[Y, UV, None]] reconstructed (padded) pictures, "frames_coded": the decoded [L_t / H_t, L_tc /
+    H_tc, mv_hat] entries decode_gop consumed}.  A missing, truncated or surplus-length file raises a ValueError that
+    names it."""
+    import struct
+    if ll_order not in LL_ORDERS:
+        raise ValueError(f"ll_order must be one of {LL_ORDERS}")
+    pairs = gop_pairs(gop)
+    stages = pairs[-1][0] + 1
+    pad_h = -(-pic_height // psize) * psize
+    pad_w = -(-pic_width // psize) * psize
+    files, names, slots = [], [], []
+
+    def picture(name, chroma, low, me_num, slot):
+        path = os.path.join(bin_folder, name)
+        data = _read_framed(path, 16)
+        h, w, n = struct.unpack(">III", data[:12])
+        want = (pic_height // 2, pic_width // 2, 2) if chroma else (pic_height, pic_width, 1)
+        if (h, w, n) != want:
+            raise ValueError(f"{path}: header says {n} plane(s) of {h}x{w}, expected {want[2]} of {want[0]}x{want[1]}")
+        files.append((data, chroma, low, me_num))
+        names.append(path)
+        slots.append(slot)
+
+    motion = []
+    for stage, i_ref, i_cur in pairs:
+        me_num = min(codec.num_me_stages - 1, stage)
+        picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
+        picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
+        path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
+        motion.append((stage, i_cur, me_num, path, _read_framed(path, 6)[6:]))
+    picture("0_main.bin", False, True, 0, (0, 0))
+    picture("0_C_main.bin", True, True, 0, (0, 1))
+
+    with torch.no_grad():
+        begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, names)
+        frames_coded = [[None, None, None] for _ in range(gop)]
+        dpb, at_stage = None, None
+        try:
+            for stage, i_cur, me_num, path, string in motion:
+                if stage != at_stage:
+                    dpb, at_stage = {"mv_feature": None, "ref_mv_y": None}, stage
+                try:
+                    d = codec.decompress_mv(string, torch.float32, pad_h // me_downsample, pad_w // me_downsample, dpb,
+                                            stage_idx=me_num, q_index=q_index, me_downsample=me_downsample)
+                except (ValueError, RuntimeError) as e:
+                    raise ValueError(f"{path}: {e}") from e
+                frames_coded[i_cur][2] = d["mv_hat"]
+                dpb = {"mv_feature": d["mv_feature"], "ref_mv_y": d["mv_y_hat"]}
+        finally:
+            # the picture files are finished (and their threads and streams drained) whatever the motion files did
+            planes = codec._decompress_gop_files_end(begun)
+        for (i, c), plane in zip(slots, planes):
+            frames_coded[i][c] = plane
+        coded = [list(fc) for fc in frames_coded]
+        rec = decode_gop(codec, frames_coded, luma_stage0=luma_stage0)
+    return {"frames": rec, "frames_coded": coded, "stages": stages}
+
+
+def frames_to_u8(frames_rec, pic_height, pic_width):
+    """reconstructed (padded, float) pictures -> [(Y, Cb, Cr)] uint8 arrays of the un-padded size: one conversion launch
+    per plane tensor (pmctf_planes_to_u8) and one copy of bytes to the host"""
+    from pMCTF.hip import ops
+    out = []
+    for rec_y, rec_c, _ in frames_rec:
+        y = ops.planes_to_u8(rec_y.contiguous(), pic_height, pic_width)
+        c = ops.planes_to_u8(rec_c.contiguous(), pic_height // 2, pic_width // 2)
+        out.append((y, c))
+    host = [(y.cpu().numpy(), c.cpu().numpy()) for y, c in out]
+    return [(y[0], c[0], c[1]) for y, c in host]
+
+
+def decode_sequence(codec, bin_folder, yuv_out, device=None):
+    """Decode a folder written by encode_sequence(keep_gops=True) into a planar 8-bit 4:2:0 file (the layout YUVReader
+    reads), GOP by GOP.  The codec holds the weights the sequence was coded with; its number of motion stages, arithmetic
+    profile and ATen thread setting must equal the header's (ValueError otherwise).  device: checked against the
+    codec's, if given.  Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP}."""
+    import time
+    header = read_sequence_header(bin_folder)
+    check_sequence_header(header, codec_header_fields(codec))
+    dev = codec.engine().dev
+    if device is not None and torch.device(device).type != dev.type:
+        raise ValueError(f"the codec lives on {dev}, not on {device}")
+    h, w = header["height"], header["width"]
+    shapes, seconds = [], []
+    with open(yuv_out, "wb") as f:
+        for k in range(header["frame_num"] // header["gop"]):
+            t0 = time.time()
+            out = decode_gop_files(codec, os.path.join(bin_folder, gop_folder(k)), header["gop"], h, w, header["q_index"],
+                                   psize=header["psize"], me_downsample=header["me_downsample"],
+                                   ll_order=header["ll_order"])
+            for planes in frames_to_u8(out["frames"], h, w):
+                for p in planes:
+                    f.write(p.tobytes(order="C"))
+                shapes.append((h, w))
+            seconds.append(time.time() - t0)
+    return {"header": header, "frames": shapes, "seconds": seconds}
