@@ -399,6 +399,31 @@ int pmctf_mv_fourpart_estimate_f32(const float *y, const float *common, const fl
 /* nn.MSELoss numerator (pMCTF_L.py:351,373; pWave.py:309): sum += sum((a[i]-b[i])^2) */
 int pmctf_sqdiff_sum_f32(const float *a, const float *b, int64_t n, double *sum, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Picture quality of one frame, what the evaluation harness reports (test_pMCTF_flex.py:293-327): squared-error sums
+ * behind Y-, Cb-, Cr- and RGB-PSNR, and the map means behind MS-SSIM of the rounded RGB pictures.
+ *   rec_y (1,1,Hp,Wp), rec_c (2,1,Hp/2,Wp/2): the reconstruction as the temporal synthesis returns it (padded, neither
+ *   clamped nor rounded); taken as rint(clamp(v, 0, 255)) (ties to even, NaN -> 0) and cropped to the top-left h x w.
+ *   org_y (1,1,h,w), org_c (2,1,h/2,w/2): the un-padded originals (integers).  h, w even; h <= Hp, w <= Wp.
+ *   Chroma is up-sampled x2 bilinearly (align_corners=False) and both pictures go through ycbcr2rgb
+ *   (pMCTF/utils/util.py) in float32 in its written order, then rint, no clamp.
+ *   out[0..3]: sums of squared differences of Y, Cb, Cr and of the three RGB planes together — integers, exact.
+ *   msssim != 0: out[4 + 6*s + 2*c + k], s = scale 0..4, c = R,G,B, k = 0: spatial mean of the contrast-structure map
+ *   cs, k = 1: of the ssim map (11-tap Gaussian window, sigma 1.5, no padding; C1 = 2.55^2, C2 = 7.65^2; 2x2 average
+ *   pool with zero padding of size % 2 between scales).  Needs min(h, w) > 160, PMCTF_EINVAL otherwise.  The final
+ *   product  mean_c( prod_{s<4} relu(cs_s)^w_s * relu(ssim_4)^w_4 )  is left to the caller (15 numbers).
+ *   msssim == 0: out[4..] is not written.
+ *   scratch: pmctf_msssim_scratch_floats(h, w) floats (PMCTF_QUALITY_FRONT_FLOATS are enough when msssim == 0), 8-byte
+ *   aligned, no initial contents required; out: PMCTF_QUALITY_OUT_DOUBLES doubles.  Both on the device.
+ *   Per-workgroup partial sums are added in a fixed order: the same input gives the same bits on every run.
+ *   Launches: 1 (front end) + 5 (one per scale, if msssim) + 1 (final sums); no memset, no synchronisation.
+ * pmctf_msssim_scratch_floats: PMCTF_EINVAL for non-positive, odd or > 16384 sizes. */
+#define PMCTF_QUALITY_FRONT_FLOATS 8192
+#define PMCTF_QUALITY_OUT_DOUBLES 34
+int64_t pmctf_msssim_scratch_floats(int h, int w);
+int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, const float *org_y, const float *org_c, int Hp, int Wp,
+                            int h, int w, int msssim, float *scratch, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

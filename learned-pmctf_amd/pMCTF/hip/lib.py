@@ -76,6 +76,8 @@ _SIGS = {
     "pmctf_z_symbols_f32": (ci, [vp] * 4 + [ci, ci, vp]),
     "pmctf_mv_fourpart_step_f32": (ci, [vp] * 6 + [ci, ci, ci, cf, cf, vp]),
     "pmctf_mv_dequant_f32": (ci, [vp, vp, vp, i64, vp]),
+    "pmctf_msssim_scratch_floats": (i64, [ci, ci]),
+    "pmctf_frame_quality_f32": (ci, [vp] * 4 + [ci] * 5 + [vp, vp, vp]),
 }
 
 

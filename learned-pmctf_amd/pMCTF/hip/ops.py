@@ -520,3 +520,65 @@ def mv_fourpart_estimate(y, common, sp, so_far, t, bits):
 def sqdiff_sum(a, b, acc):
     assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
     _lib.check(_lib.hip().pmctf_sqdiff_sum_f32(_p(a), _p(b), a.numel(), _pd(acc), _stream()), "sqdiff_sum")
+
+
+# ------------------------------------------------------------------------------------------------
+# picture quality (csrc/quality_ops.hip)
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MSSSIM_MIN_SIDE = 160                   # (11 - 1) * 2^4: the smaller side must exceed it
+QUALITY_FRONT_FLOATS, QUALITY_OUT_DOUBLES = 8192, 34        # PMCTF_QUALITY_* of include/pmctf_hip.h
+
+
+def msssim_from_means(means):
+    """means[s][c] = (mean cs, mean ssim) of scale s, channel c -> MS-SSIM: per channel the product of relu(cs_s)^w_s over
+    scales 0..3 and relu(ssim_4)^w_4, then the mean over the channels; float64 on the host"""
+    total = 0.0
+    for c in range(3):
+        v = 1.0
+        for s, wgt in enumerate(MSSSIM_WEIGHTS):
+            v *= max(float(means[s][c][1 if s == len(MSSSIM_WEIGHTS) - 1 else 0]), 0.0) ** wgt
+        total += v
+    return total / 3.0
+
+
+def _psnr_from_sse(sse, n):
+    import math
+    return math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * n / sse)
+
+
+def frame_quality(rec_y, rec_c, org_y, org_c, h, w, msssim=True, return_means=False):
+    """Quality of one reconstructed frame as the harness reports it (test_pMCTF_flex.py:293-327): rec_y (1,1,Hp,Wp) /
+    rec_c (2,1,Hp/2,Wp/2) padded, neither clamped nor rounded; org_y (1,1,h,w) / org_c (2,1,h/2,w/2) the originals.
+    -> {"y","cb","cr","yuv","rgb": PSNR in dB (inf for identical pictures), "msssim", "sse": (Y, Cb, Cr, RGB) ints}.
+    msssim: 0.0 when not asked for or when min(h, w) <= 128 (the harness's own guard); ValueError for
+    128 < min(h, w) <= 160, where five scales do not fit.  One device->host copy.  return_means adds "means"
+    [5][3][2] (scale, channel, (cs, ssim)), None without MS-SSIM."""
+    h, w = int(h), int(w)
+    rec_y, rec_c, org_y, org_c = (t.contiguous() for t in (rec_y, rec_c, org_y, org_c))
+    Hp, Wp = rec_y.shape[-2:]
+    if h <= 0 or w <= 0 or (h | w) & 1 or h > Hp or w > Wp:
+        raise ValueError(f"picture size {h}x{w} must be even, positive and inside the padded {Hp}x{Wp}")
+    if tuple(rec_c.shape) != (2, 1, Hp // 2, Wp // 2) or tuple(org_y.shape[-2:]) != (h, w) or \
+            tuple(org_c.shape) != (2, 1, h // 2, w // 2) or rec_y.numel() != Hp * Wp or org_y.numel() != h * w:
+        raise ValueError("expect luma (1,1,Hp,Wp) / chroma (2,1,Hp/2,Wp/2) reconstructions and un-padded originals")
+    with_ms = bool(msssim) and min(h, w) > 128
+    if with_ms and min(h, w) <= MSSSIM_MIN_SIDE:
+        raise ValueError(f"MS-SSIM with five scales needs a smaller side above {MSSSIM_MIN_SIDE}, got {h}x{w}")
+    L = _lib.hip()
+    n_scratch = L.pmctf_msssim_scratch_floats(h, w) if with_ms else QUALITY_FRONT_FLOATS
+    scratch = torch.empty(n_scratch, dtype=torch.float32, device=rec_y.device)
+    out = torch.empty(QUALITY_OUT_DOUBLES, dtype=torch.float64, device=rec_y.device)
+    _lib.check(L.pmctf_frame_quality_f32(_p(rec_y), _p(rec_c), _p(org_y), _p(org_c), Hp, Wp, h, w, int(with_ms),
+                                         _p(scratch), _pd(out), _stream()), "frame_quality")
+    host = out.cpu().tolist()                               # the frame's one copy to the host
+    sse = tuple(int(v) for v in host[:4])
+    assert all(float(s) == v for s, v in zip(sse, host[:4])), "squared-error sums are integers"
+    n = h * w
+    res = {"y": _psnr_from_sse(sse[0], n), "cb": _psnr_from_sse(sse[1], n // 4), "cr": _psnr_from_sse(sse[2], n // 4),
+           "rgb": _psnr_from_sse(sse[3], 3 * n), "sse": sse}
+    res["yuv"] = (6.0 * res["y"] + res["cb"] + res["cr"]) / 8.0
+    means = [[(host[4 + 6 * s + 2 * c], host[5 + 6 * s + 2 * c]) for c in range(3)] for s in range(5)] if with_ms else None
+    res["msssim"] = msssim_from_means(means) if with_ms else 0.0
+    if return_means:
+        res["means"] = means
+    return res

@@ -214,6 +214,25 @@ def gop_psnr(frames_rec, frames_orig, pic_height, pic_width):
     return out
 
 
+def gop_quality(frames_rec, frames_orig, pic_height, pic_width, msssim=True):
+    """gop_psnr + rgb_psnr + MS-SSIM of the rounded RGB pictures (test_pMCTF_flex.py:293-327) per frame, from the HIP
+    quality kernels (pMCTF.hip.ops.frame_quality): a handful of launches and ONE device->host copy per frame, exact
+    integer error sums, float64 PSNR.  frames_rec: [[Y, UV, ...]] as decode_gop returns them (padded, not clamped);
+    frames_orig: the un-padded originals of read_gop.  -> [{"y","cb","cr","yuv","rgb","msssim","sse"}].
+    msssim is 0.0 when not asked for or for pictures with a side of 128 or less (the harness's guard), and a ValueError
+    for a smaller side of 129..160.  Like the rest of the product path there is no CPU fallback."""
+    from pMCTF.hip import ops
+    out = []
+    for rec, (y, c) in zip(frames_rec, frames_orig):
+        tensors = (rec[0], rec[1], y, c)
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+            raise RuntimeError("gop_quality runs on the GPU (no CPU fallback): pass device tensors, or use gop_psnr / "
+                               "rgb_psnr for tensors on the host")
+        rec_y, rec_c, y, c = (t.float().contiguous() for t in tensors)
+        out.append(ops.frame_quality(rec_y, rec_c, y, c, pic_height, pic_width, msssim=msssim))
+    return out
+
+
 def write_yuv(path, frames_u8):
     """[(Y, Cb, Cr) uint8 arrays] -> planar 8-bit 4:2:0 file, the layout YUVReader / image_import read"""
     with open(path, "wb") as f:
@@ -250,15 +269,18 @@ def rgb_psnr(rec_y, rec_c, y, c):
 
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                    skip_decoding=True, psize=128, keep_gops=False):
+                    skip_decoding=True, psize=128, keep_gops=False, msssim=False):
     """What the evaluation harness produces for one sequence (test_pMCTF_flex.py:run_test, 86-346) built from this
     module's own pieces: pictures come from a planar .yuv through YUVReader and get_padding_size, every closed GOP goes
     through encode_gop (one encode_one_stage call per pair, both per-pair report lines), decode_gop and gop_psnr, and
-    the per-frame tables are folded into the harness's log record by generate_log_json / dump_json.  MS-SSIM is
-    reported as 0 (pytorch_msssim is a third-party package the harness imports; not part of the path).
+    the per-frame tables are folded into the harness's log record by generate_log_json / dump_json.
+    msssim=False (default): PSNR from gop_psnr / rgb_psnr, MS-SSIM reported as 0 — the record the fixtures hold.
+    msssim=True: the per-frame quality comes from gop_quality (HIP kernels, no third-party package): frame_msssim and the
+    ave_*_msssim fields of the record are filled, and the result gains "msssim".  Pictures need a smaller side above 160
+    (0 is reported, as by the harness, when a side is 128 or less).
     keep_gops=True: GOP k goes to bin_folder/gop_{k:05d}/ instead of overwriting GOP k-1's files, and bin_folder gets the
     sequence.json header decode_sequence needs (write_sequence_header).
-    Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"}."""
+    Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
     import io
     import time
     from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
@@ -267,6 +289,7 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     reader = YUVReader(yuv_path, width, height, start_index=0)
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines = []
+    ssims = []
     pairs = 0
     seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
     t0 = time.time()
@@ -284,11 +307,15 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                     seconds[k] += r[k]
             lines += enc["log"]
             rec = decode_gop(codec, enc["frames_coded"])
-            quality = gop_psnr(rec, orig, h, w)
+            quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
             tables["bits"] += enc["bits"]
             tables["bpp_mv"] += [b / (h * w) for b in enc["bits_mv"]]
             tables["psnr"] += [p["yuv"] for p in quality]
             tables["frame_types"] += [0] + [1] * (gop - 1)          # the one coded L picture of a GOP, then its H pictures
+            if msssim:
+                tables["psnr_rgb"] += [p["rgb"] for p in quality]
+                ssims += [p["msssim"] for p in quality]
+                continue
             for (ry, rc, _), (y, c) in zip(rec, orig):
                 crop_y = torch.round(ry.clamp(0, 255.0))[:, :, :h, :w]
                 crop_c = torch.round(rc.clamp(0, 255.0))[:, :, :h // 2, :w // 2]
@@ -301,10 +328,61 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
         lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
     record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
-                               tables["psnr_rgb"], [0] * frame_num, height * width, time.time() - t0)
+                               tables["psnr_rgb"], ssims if msssim else [0] * frame_num, height * width, time.time() - t0)
     text = io.StringIO()
     dump_json(record, text, float_digits=6, indent=2)
-    return dict(tables, log=record, json=text.getvalue(), lines=lines)
+    out = dict(tables, log=record, json=text.getvalue(), lines=lines)
+    if msssim:
+        out["msssim"] = ssims
+    return out
+
+
+def quality_line(idx, q, bpp=None, seconds=None):
+    """one frame's report line in the harness's wording (test_pMCTF_flex.py:330-332); the coding time and rate are left
+    out where there is none (two files compared)"""
+    head = f"frame {idx}" + ("" if seconds is None else f", {seconds:.3f} seconds") + ","
+    rate = "" if bpp is None else f"bpps: {bpp:.3f}, "
+    return (f"{head} {rate}YUV-PSNR: {q['yuv']:.4f}, RGB-PSNR: {q['rgb']:.4f},MS-SSIM: {q['msssim']:.4f}, "
+            f"Y-PSNR: {q['y']:.4f},  Cb-PSNR: {q['cb']:.4f}, Cr-PSNR: {q['cr']:.4f}  ")
+
+
+def sequence_quality(src_yuv, rec_yuv, width, height, frame_num, device, gop=None, msssim=True):
+    """Quality of a decoded planar 8-bit 4:2:0 file against its source, frame by frame, through YUVReader and gop_quality
+    (the files -> .yuv -> quality end of the loop decode_sequence opens).
+    -> {"psnr" (YUV), "psnr_rgb", "msssim", "psnr_y", "psnr_cb", "psnr_cr": per-frame lists, "sse": [(Y, Cb, Cr, RGB)],
+        "mean": {table: mean}, "frame_types": [0] + [1] * (gop - 1) per GOP when gop is given (as encode_sequence), else
+        None, "lines": one report line per frame}."""
+    from pMCTF.utils.yuv_reader import YUVReader
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("sequence_quality runs on the GPU (no CPU fallback)")
+    if width <= 0 or height <= 0 or (width | height) & 1 or frame_num <= 0:
+        raise ValueError(f"4:2:0 pictures have even, positive sizes (got {width}x{height}, {frame_num} frames)")
+    if gop is not None and (gop < 1 or frame_num % gop):
+        raise ValueError(f"frame_num {frame_num} is not a multiple of gop {gop}")
+    frame_bytes = width * height + 2 * (width // 2) * (height // 2)
+    for path in (src_yuv, rec_yuv):
+        if os.path.getsize(path) < frame_num * frame_bytes:
+            raise ValueError(f"{path}: shorter than {frame_num} pictures of {width}x{height}")
+    ro, rd = YUVReader(src_yuv, width, height, start_index=0), YUVReader(rec_yuv, width, height, start_index=0)
+    names = {"yuv": "psnr", "rgb": "psnr_rgb", "msssim": "msssim", "y": "psnr_y", "cb": "psnr_cb", "cr": "psnr_cr"}
+    out = {v: [] for v in names.values()}
+    out.update(sse=[], lines=[])
+    try:
+        for idx in range(frame_num):
+            # psize=2: nothing to pad (the sizes are even), the pictures go to the kernels as they are in the files
+            _, orig, (h, w) = read_gop(ro, 1, device, psize=2)
+            _, dec, _ = read_gop(rd, 1, device, psize=2)
+            q = gop_quality([(dec[0][0], dec[0][1], None)], orig, h, w, msssim=msssim)[0]
+            for k, v in names.items():
+                out[v].append(q[k])
+            out["sse"].append(q["sse"])
+            out["lines"].append(quality_line(idx, q))
+    finally:
+        ro.close()
+        rd.close()
+    out["mean"] = {v: sum(out[v]) / frame_num for v in names.values()}
+    out["frame_types"] = None if gop is None else ([0] + [1] * (gop - 1)) * (frame_num // gop)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- decoding from files
