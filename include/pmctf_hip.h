@@ -424,6 +424,35 @@ int64_t pmctf_msssim_scratch_floats(int h, int w);
 int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, const float *org_y, const float *org_c, int Hp, int Wp,
                             int h, int w, int msssim, float *scratch, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * DIAGNOSTIC entry point; the codec never calls it.  Evaluates one of the scalar functions behind every kernel above
+ * (csrc/pm_device_math.h, pm_sleef_f32.h, pm_glibc_expf.h) on n float32 bit patterns, as the GPU compiler built them:
+ * y[i] = fn(bits[i]), or fn(first_bits + i) (mod 2^32) when bits == NULL, so that all 2^32 inputs can be swept without
+ * an input array.  The suite compares it with the oracle on every float32 (tests/test_gpu_math_sweep.py).
+ *   fn: PMCTF_PROBE_TANH        tanh, interval table read from global memory   (torch.tanh, lifting_1d.py:39,42)
+ *       PMCTF_PROBE_TANH_LDS    tanh, table copied to LDS by the workgroup
+ *       PMCTF_PROBE_SIGMOID     1 / (1 + Sleef_expf(-x))                        (torch.sigmoid, long_context.py:24)
+ *       PMCTF_PROBE_SIGMOID_SCALAR  1 / (1 + expf(-x)), glibc's expf: ATen's scalar tail
+ *       PMCTF_PROBE_LOG         log as the CDF-row index takes it               (torch.log, entropy_models.py:271)
+ *       PMCTF_PROBE_LOG_POLY    its polynomial schedule outside [2^-100, 2^100), on every input
+ *       PMCTF_PROBE_EXP         exp of the estimate-mode kernels
+ *       PMCTF_PROBE_GLIBC_EXP   the transcription of glibc's expf alone
+ *       PMCTF_PROBE_ACT + PMCTF_ACT_{RELU,LEAKY,TANH,SIGMOID}   the conv epilogue's activation; `slope` is the leaky slope
+ *   (ignored by every other fn).
+ * bits (may be NULL), y: device pointers; y 16-byte aligned (four results per store).  0 < n <= 2^32.
+ * PMCTF_EINVAL, before any launch, for a null or misaligned y, n out of range and an unknown fn. */
+#define PMCTF_PROBE_TANH 0
+#define PMCTF_PROBE_TANH_LDS 1
+#define PMCTF_PROBE_SIGMOID 2
+#define PMCTF_PROBE_SIGMOID_SCALAR 3
+#define PMCTF_PROBE_LOG 4
+#define PMCTF_PROBE_LOG_POLY 5
+#define PMCTF_PROBE_EXP 6
+#define PMCTF_PROBE_GLIBC_EXP 7
+#define PMCTF_PROBE_ACT 8
+int pmctf_math_probe_f32(int fn, const uint32_t *bits, uint32_t first_bits, int64_t n, float *y, float slope,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,11 +14,11 @@ typedef float pm_f32x4 __attribute__((ext_vector_type(4)));
 template <int ACT>
 __device__ __forceinline__ float act_c(float v, int act, float slope) {
     if constexpr (ACT == pm::ACT_NONE) return v;
-    else if constexpr (ACT == pm::ACT_RELU) return v > 0.0f ? v : 0.0f;
+    else if constexpr (ACT == pm::ACT_RELU) return pm::relu_(v);
     else if constexpr (ACT == pm::ACT_LEAKY) return v > 0.0f ? v : v * slope;
     else if constexpr (ACT == -2) {
         switch (act) {
-        case pm::ACT_RELU: return v > 0.0f ? v : 0.0f;
+        case pm::ACT_RELU: return pm::relu_(v);
         case pm::ACT_LEAKY: return v > 0.0f ? v : v * slope;
         default: return v;
         }

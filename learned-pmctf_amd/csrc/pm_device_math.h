@@ -86,8 +86,10 @@ __device__ __forceinline__ void tanh_rows_to_lds(uint4 *dst, int tid, int nthrea
     for (int i = tid; i < TANH_LDS_UINT4; i += nthreads) dst[i] = src[i];
 }
 
-// torch.sigmoid of a float CPU tensor: 1 / (1 + Sleef_expf16_u10(0 - x)), transcribed in pm_sleef_f32.h
-__device__ __forceinline__ float sigmoidf_(float x) { return pm_aten_sigmoidf(x); }
+// torch.sigmoid of a float CPU tensor: 1 / (1 + Sleef_expf16_u10(0 - x)), transcribed in pm_sleef_f32.h.  A NaN comes back
+// quieted with its own sign, as x86's 0 - x leaves it; the GPU's subtraction negates its second operand, NaN or not, and
+// handed every NaN back with the sign flipped (found by the sweep of all 2^32 inputs, tests/test_gpu_math_sweep.py).
+__device__ __forceinline__ float sigmoidf_(float x) { return x != x ? x + x : pm_aten_sigmoidf(x); }
 
 // natural log: the schedule of Intel MKL's vmsLn (high accuracy, AVX-512 kernel) = torch.log on a float32 CPU tensor, bit
 // for bit on [2^-100, 2^100) (oracle/c/pm_math.h pm_logf has the derivation; tools/mkl_log_tables.py --verify the check);
@@ -146,9 +148,12 @@ __device__ __forceinline__ float logf_(float x) {
 // activations used in conv epilogues
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_TANH = 3, ACT_SIGMOID = 4 };
 
+// torch.relu on a float CPU tensor, bit for bit: max(0, v) as x86's maxps takes it — a NaN and -0 come back as they are
+__device__ __forceinline__ float relu_(float v) { return v < 0.0f ? 0.0f : v; }
+
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
     switch (act) {
-    case ACT_RELU: return v > 0.0f ? v : 0.0f;            // torch.relu: max(v,0); -0 -> 0 numerically equal
+    case ACT_RELU: return relu_(v);
     case ACT_LEAKY: return v > 0.0f ? v : v * slope;      // F.leaky_relu
     case ACT_TANH: return tanhf_(v);
     case ACT_SIGMOID: return sigmoidf_(v);

@@ -78,6 +78,7 @@ _SIGS = {
     "pmctf_mv_dequant_f32": (ci, [vp, vp, vp, i64, vp]),
     "pmctf_msssim_scratch_floats": (i64, [ci, ci]),
     "pmctf_frame_quality_f32": (ci, [vp] * 4 + [ci] * 5 + [vp, vp, vp]),
+    "pmctf_math_probe_f32": (ci, [ci, vp, C.c_uint32, i64, vp, cf, vp]),          # diagnostic: never on the codec's path
 }
 
 

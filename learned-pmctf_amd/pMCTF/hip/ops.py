@@ -582,3 +582,25 @@ def frame_quality(rec_y, rec_c, org_y, org_c, h, w, msssim=True, return_means=Fa
     if return_means:
         res["means"] = means
     return res
+
+
+# ------------------------------------------------------------------------------------------------
+# diagnostic (csrc/math_probe.hip): the device's scalar functions on raw float32 bit patterns; never on the codec's path
+PROBE_TANH, PROBE_TANH_LDS, PROBE_SIGMOID, PROBE_SIGMOID_SCALAR, PROBE_LOG, PROBE_LOG_POLY, PROBE_EXP, \
+    PROBE_GLIBC_EXP, PROBE_ACT = range(9)                    # PMCTF_PROBE_* of include/pmctf_hip.h; PROBE_ACT + ACT_*
+
+
+def math_probe(fn, bits=None, first_bits=0, n=None, slope=0.0, out=None, device="cuda"):
+    """y[i] = fn(bits[i]) for an int32 / uint32-as-int32 device tensor `bits`, or fn(first_bits + i) (mod 2^32) for
+    i < n when bits is None.  Returns a float32 tensor of n results (view its bits with .view(torch.int32))."""
+    if bits is not None:
+        assert bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and bits.dim() == 1
+        n, device = bits.numel(), bits.device
+    n = int(n)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    _lib.check(_lib.hip().pmctf_math_probe_f32(int(fn), None if bits is None else C.c_void_p(bits.data_ptr()),
+                                               int(first_bits) & 0xffffffff, n, _p(out), float(slope), _stream()),
+               "math_probe")
+    return out[:n]

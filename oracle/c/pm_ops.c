@@ -278,25 +278,48 @@ void pm_dwconv2d(const float *x, const float *w, const float *bias, float *y,
     }
 }
 
-/* elementwise transcendental maps (see pm_math.h) */
-void pm_tanh_arr(const float *x, float *y, long n) {
-    for (long i = 0; i < n; ++i) y[i] = pm_tanhf(x[i]);
-}
-void pm_sigmoid_arr(const float *x, float *y, long n) {
-    for (long i = 0; i < n; ++i) y[i] = pm_sigmoidf(x[i]);
-}
+/* elementwise transcendental maps (see pm_math.h): blocks of PM_MAP_BLOCK elements through pm_parallel_for — every
+ * element is computed by the same scalar function whatever the thread count, so results do not depend on it */
+#define PM_MAP_BLOCK 65536L
+typedef struct { const float *x; float *y; long n; int threads; } pm_map_ctx;
+#define PM_MAP(NAME, EXPR)                                                                              \
+    static void NAME##_job(long job, void *vctx) {                                                      \
+        const pm_map_ctx *c = (const pm_map_ctx *)vctx;                                                 \
+        const float *x = c->x; float *y = c->y; const long n = c->n; const int threads = c->threads;    \
+        (void)threads;                                                                                  \
+        const long b = job * PM_MAP_BLOCK, e = b + PM_MAP_BLOCK < n ? b + PM_MAP_BLOCK : n;             \
+        for (long i = b; i < e; ++i) y[i] = (EXPR);                                                     \
+    }                                                                                                   \
+    static void NAME##_run(const float *x, float *y, long n, int threads) {                             \
+        pm_map_ctx c = {x, y, n, threads};                                                              \
+        if (n > 0) pm_parallel_for((n + PM_MAP_BLOCK - 1) / PM_MAP_BLOCK, 1, NAME##_job, &c);           \
+    }
+PM_MAP(pm_tanh_map, pm_tanhf(x[i]))
+PM_MAP(pm_sigmoid_map, pm_sigmoidf(x[i]))
+PM_MAP(pm_sigmoid_aten_map,
+       (threads > 0 && pm_aten_sigmoid_tail(i, n, threads)) ? pm_aten_sigmoidf_scalar(x[i]) : pm_sigmoidf(x[i]))
+PM_MAP(pm_sigmoid_scalar_map, pm_aten_sigmoidf_scalar(x[i]))
+PM_MAP(pm_log_map, pm_logf(x[i]))
+PM_MAP(pm_log_poly_map, pm_logf_poly(x[i]))
+PM_MAP(pm_exp_map, pm_expf(x[i]))
+PM_MAP(pm_glibc_exp_map, pm_glibc_expf(x[i]))
+PM_MAP(pm_libm_exp_map, expf(x[i]))
+
+void pm_tanh_arr(const float *x, float *y, long n) { pm_tanh_map_run(x, y, n, 0); }
+void pm_sigmoid_arr(const float *x, float *y, long n) { pm_sigmoid_map_run(x, y, n, 0); }
 /* torch.sigmoid of a contiguous tensor as ATen evaluates it with `threads` intra-op threads: SLEEF on whole strides of 32
  * floats of every thread's slice, libm's expf on the rest of a slice (pm_glibc_expf.h) */
-void pm_sigmoid_aten_arr(const float *x, float *y, long n, int threads) {
-    for (long i = 0; i < n; ++i)
-        y[i] = (threads > 0 && pm_aten_sigmoid_tail(i, n, threads)) ? pm_aten_sigmoidf_scalar(x[i]) : pm_sigmoidf(x[i]);
-}
-void pm_log_arr(const float *x, float *y, long n) {
-    for (long i = 0; i < n; ++i) y[i] = pm_logf(x[i]);
-}
-void pm_exp_arr(const float *x, float *y, long n) {
-    for (long i = 0; i < n; ++i) y[i] = pm_expf(x[i]);
-}
+void pm_sigmoid_aten_arr(const float *x, float *y, long n, int threads) { pm_sigmoid_aten_map_run(x, y, n, threads); }
+/* the scalar lambda alone, on every element: 1 / (1 + pm_glibc_expf(-x)) */
+void pm_sigmoid_scalar_arr(const float *x, float *y, long n) { pm_sigmoid_scalar_map_run(x, y, n, 0); }
+void pm_log_arr(const float *x, float *y, long n) { pm_log_map_run(x, y, n, 0); }
+/* the polynomial schedule pm_logf uses outside [2^-100, 2^100), on every element */
+void pm_log_poly_arr(const float *x, float *y, long n) { pm_log_poly_map_run(x, y, n, 0); }
+void pm_exp_arr(const float *x, float *y, long n) { pm_exp_map_run(x, y, n, 0); }
+/* the transcription of glibc's expf (pm_glibc_expf.h), and the expf of the libm this library is linked against: what the
+ * transcription is measured with (tests/test_math_sweep_cpu.py) */
+void pm_glibc_exp_arr(const float *x, float *y, long n) { pm_glibc_exp_map_run(x, y, n, 0); }
+void pm_libm_exp_arr(const float *x, float *y, long n) { pm_libm_exp_map_run(x, y, n, 0); }
 
 /* ---------------------------------------------------------------------------
  * flow_warp: pMCTF/layers/video/video_net.py:32-55 (torch_warp) =

@@ -35,7 +35,8 @@ def lib():
     L.pm_conv2d.argtypes = [f32p, f32p, C.c_void_p, f32p] + [C.c_int] * 10
     L.pm_conv2d_rule.argtypes = [f32p, f32p, C.c_void_p, f32p] + [C.c_int] * 11
     L.pm_dwconv2d.argtypes = [f32p, f32p, C.c_void_p, f32p] + [C.c_int] * 5
-    for n in ("pm_tanh_arr", "pm_sigmoid_arr", "pm_log_arr", "pm_exp_arr"):
+    for n in ("pm_tanh_arr", "pm_sigmoid_arr", "pm_log_arr", "pm_exp_arr", "pm_sigmoid_scalar_arr", "pm_log_poly_arr",
+              "pm_glibc_exp_arr", "pm_libm_exp_arr"):
         getattr(L, n).argtypes = [f32p, f32p, C.c_long]
     L.pm_sigmoid_aten_arr.argtypes = [f32p, f32p, C.c_long, C.c_int]
     L.pm_flow_warp.argtypes = [f32p, f32p, f32p, f32p, f32p] + [C.c_int] * 5
@@ -139,6 +140,26 @@ def log(x):
 
 def exp(x):
     return _map("pm_exp_arr", x)
+
+
+def sigmoid_scalar(x):
+    """ATen's scalar sigmoid lambda on every element: 1 / (1 + pm_glibc_expf(-x))"""
+    return _map("pm_sigmoid_scalar_arr", x)
+
+
+def log_poly(x):
+    """the polynomial schedule log() uses outside [2^-100, 2^100), on every element"""
+    return _map("pm_log_poly_arr", x)
+
+
+def glibc_exp(x):
+    """the transcription of glibc's expf (oracle/c/pm_glibc_expf.h)"""
+    return _map("pm_glibc_exp_arr", x)
+
+
+def libm_exp(x):
+    """expf of the libm the oracle library is linked against"""
+    return _map("pm_libm_exp_arr", x)
 
 
 def flow_warp(im, flow, lin_x, lin_y):

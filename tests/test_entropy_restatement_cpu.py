@@ -276,9 +276,10 @@ def test_every_entry_point_refuses_what_its_guard_lists():
             assert getattr(L, name)(*a) == -1, (name, "params_sub on an odd plane")
 
 
-# what else csrc/ew_ops.hip and csrc/decode_ops.hip export: layout / network kernels and the sequential LL decoder, which
-# have direct tests of their own (test_gpu_kernels.py, test_gpu_ll_decode.py), and the two CDF-row kernels of the decoder
-# (test_scale_index_rows_at_every_gpu_site)
+# what else csrc/ew_ops.hip and csrc/decode_ops.hip export: layout / network kernels, each reached by name through its ops
+# wrapper in a tests/test_gpu_*.py (test_math_sweep_cpu.py::test_every_layout_and_network_kernel_has_a_direct_gpu_test
+# keeps that true), the sequential LL decoder (test_gpu_ll_decode.py), and the two CDF-row kernels of the decoder
+# (test_scale_index_rows_at_every_gpu_site, test_gpu_math_sweep.py::test_cdf_row_of_every_scale)
 OTHER_EXPORTS = {
     "ew_ops": {"pmctf_ew_f32", "pmctf_spynet_pack8_f32", "pmctf_lift_skip3_f32", "pmctf_nearest_up2_nhwc_f32",
                "pmctf_pixel_shuffle2_nhwc_f32", "pmctf_ffn3_mix_f32", "pmctf_lstm_gates_f32", "pmctf_lstm_gates_aten_f32",

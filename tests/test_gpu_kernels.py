@@ -558,3 +558,247 @@ def test_scale_index_rows_at_every_gpu_site(cuda):
             idx = torch.zeros(16 * HW, dtype=torch.int16, device="cuda")
             ops.mv_fourpart_step(y, common, sp, torch.zeros(1, 1, HW, 64, device="cuda"), sym, idx, 0, t, lmin, lstep)
             assert_same(idx.cpu().numpy(), want_mv, f"mv_fourpart t={t}, {name}")
+
+
+# ---- kernels that had no direct test, odd sizes, and one shape past the grid cap for every grid-stride kernel -----------
+# Every grid-stride kernel of ew_ops.hip and basic_ops.hip caps its grid at 16384 workgroups of 256 threads (8192 for
+# conv_smallcin_kernel): a launch with more work items than GRID_CAP makes every thread take a second trip of its loop.
+GRID_CAP = 16384 * 256
+
+
+def assert_bits(a, b, what):
+    """assert_same on the bit patterns: tells -0 from +0"""
+    assert_same(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32), what)
+
+
+@pytest.mark.parametrize("hw", [(37, 53), (1, 7), (1152, 1920), (2100, 2000)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_spynet_pack8_is_the_concatenation(cuda, hw):
+    """spynet_pack8 against torch.cat([im1 x3, warped x3, flow_up], 1) (video_net.py:116-119) in NHWC; odd sizes, the
+    1080p level and one plane past the grid cap"""
+    from pMCTF.hip import ops
+    H, W = hw
+    r = _rng(H + W)
+    im1, wrp = (r.standard_normal((1, 1, H, W), dtype=np.float32) for _ in range(2))
+    fu = r.standard_normal((1, 2, H, W), dtype=np.float32)
+    want = np.concatenate([im1] * 3 + [wrp] * 3 + [fu], 1)
+    got = ops.spynet_pack8(*(torch.from_numpy(a).cuda() for a in (im1, wrp, fu)))
+    assert_bits(nchw(got), want, f"spynet_pack8 {H}x{W}")
+
+
+@pytest.mark.parametrize("rule", [0, 1], ids=["chain", "blocks"])
+@pytest.mark.parametrize("shape", [(1, 1, 2, 16), (2, 3, 2, 5), (1, 1, 37, 53), (2, 2, 16, 31), (1, 1, 2100, 2001)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_lift_skip3_bitexact(cuda, shape, rule):
+    """lift_skip3 against the oracle's lifting skip filter (reflection pad of one row above and below, then the 3x1
+    convolution under the same summation rule: oracle/pmctf_oracle/model.py lift_skip).  H = 2 (both reflections hit the
+    same row), several planes, odd W, and a plane of more than 4.2 M elements (past the grid cap)."""
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    n, c, H, W = shape
+    r = _rng(H * W + rule)
+    x = (r.standard_normal(shape, dtype=np.float32) * 50).astype(np.float32)
+    w3 = r.standard_normal(3, dtype=np.float32)
+    bias = np.float32(0.3125 + rule)
+    xp = np.pad(x.reshape(n * c, 1, H, W), ((0, 0), (0, 0), (1, 1), (0, 0)), mode="reflect")
+    want = clib.conv2d(xp, w3.reshape(1, 1, 3, 1), np.array([bias], np.float32), 1, (0, 0), rule).reshape(shape)
+    got = ops.lift_skip3(torch.from_numpy(x).cuda(), w3, bias, rule)
+    assert_bits(got.cpu().numpy(), want, f"lift_skip3 {shape} rule {rule}")
+
+
+@pytest.mark.parametrize("shape", [(1, 5, 7, 6), (2, 9, 4, 64), (1, 1100, 1000, 8)], ids=lambda s: "x".join(map(str, s)))
+def test_ffn3_mix_bitexact(cuda, shape):
+    """ffn3_mix against leaky(x1, 0.1) + leaky(x2, 0.01) in float32 (video/layers.py:163-167), x = [x1 | x2] on the
+    channels; zeros of both signs among the inputs; the last shape is past the grid cap"""
+    from pMCTF.hip import ops
+    n, h, w, c2 = shape
+    r = _rng(h * w)
+    x = (r.standard_normal(shape, dtype=np.float32) * 3).astype(np.float32)
+    c = c2 // 2
+    x[0, 0, 0, :] = np.float32(-0.0)                # -0 + -0 = -0
+    x[0, 0, 1, :] = np.float32(0.0)                 # +0 + +0 = +0
+    x[0, 0, 2, :c], x[0, 0, 2, c:] = np.float32(-0.0), np.float32(0.0)      # -0 + +0 = +0
+    x[0, 0, 3, :c] = np.float32(-0.0)               # -0 + anything
+    x1, x2 = x[..., :c], x[..., c:]
+    want = np.where(x1 > 0, x1, x1 * np.float32(0.1)) + np.where(x2 > 0, x2, x2 * np.float32(0.01))
+    assert (np.signbit(want) & (want == 0)).any() and (~np.signbit(want) & (want == 0)).any()
+    got = ops.ffn3_mix(torch.from_numpy(x).cuda())
+    assert n * h * w * c > GRID_CAP or shape[1] < 100
+    assert_bits(got.cpu().numpy(), want.astype(np.float32), f"ffn3_mix {shape}")
+
+
+@pytest.mark.parametrize("shape", [(3, 1, 37, 53), (3, 2, 36, 60), (3, 1, 1152, 1920)], ids=lambda s: "x".join(map(str, s)))
+def test_flow_warp_one_flow_field_per_plane(cuda, shape):
+    """flow_warp with flowN = N (one flow field per plane; test_flow_warp_bitexact shares one): N = 3, and at 1152x1920,
+    where the three planes together are past the grid cap"""
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    N, Cc, H, W = shape
+    r = _rng(17)
+    im = (r.random(shape, dtype=np.float32) * 255).astype(np.float32)
+    flow = (r.standard_normal((N, 2, H, W), dtype=np.float32) * np.array([2, 6, 12], np.float32).reshape(3, 1, 1, 1)).astype(np.float32)
+    flow[1, 0, 0, :] = 1000.0
+    flow[2, 1, :, 0] = -1000.0
+    lx = torch.linspace(-1.0, 1.0, W).numpy(); ly = torch.linspace(-1.0, 1.0, H).numpy()
+    for sign in (1.0, -1.0):
+        ref = clib.flow_warp(im, flow * np.float32(sign), lx, ly)
+        assert not np.array_equal(ref[0], clib.flow_warp(im[:1], flow[1:2] * np.float32(sign), lx, ly)[0])
+        out = ops.flow_warp(torch.from_numpy(im).cuda(), torch.from_numpy(flow).cuda(),
+                            torch.from_numpy(lx).cuda(), torch.from_numpy(ly).cuda(), sign)
+        assert_same(out.cpu().numpy(), ref, f"warp {shape} sign {sign}")
+
+
+def test_resample_odd_sizes_and_tiny_planes(cuda):
+    """avgpool2 and bilinear_down on odd H and odd W (the last row / column is dropped, as F.avg_pool2d and F.interpolate
+    do); bilinear_up x2 / x4 / x8 on a 1x1 and a 1xW plane (every source index clamps); the factor-2 entry points"""
+    import ctypes
+    from pmctf_oracle import clib
+    from pMCTF.hip import lib, ops
+    r = _rng(23)
+    for shape in ((2, 3, 37, 61), (1, 2, 36, 61), (1, 1, 37, 60), (1, 1, 3, 3), (1, 1, 9, 17)):
+        x = (r.standard_normal(shape, dtype=np.float32) * 10).astype(np.float32)
+        xt = torch.from_numpy(x).cuda()
+        assert_same(ops.avgpool2(xt).cpu().numpy(), clib.avgpool2(x), f"avgpool2 {shape}")
+        for f in (2, 4, 8):
+            if shape[2] >= f and shape[3] >= f:
+                assert_same(ops.bilinear_down2(xt, 1.0, f).cpu().numpy(), clib.bilinear_down(x, f), f"down /{f} {shape}")
+    for shape in ((1, 1, 1, 1), (2, 1, 1, 1), (1, 2, 1, 13), (1, 1, 7, 1)):
+        x = (r.standard_normal(shape, dtype=np.float32) * 10).astype(np.float32)
+        xt = torch.from_numpy(x).cuda()
+        for f in (2, 4, 8):
+            assert_same(ops.bilinear_up2(xt, 1.0, f).cpu().numpy(), clib.bilinear_up(x, f), f"up x{f} {shape}")
+    x = (r.standard_normal((1, 2, 9, 11), dtype=np.float32) * 10).astype(np.float32)        # pmctf_bilinear_{up,down}2_f32
+    xt = torch.from_numpy(x).cuda()
+    L, p = lib.hip(), lambda t: ctypes.c_void_p(t.data_ptr())
+    up, dn = torch.empty(1, 2, 18, 22, device="cuda"), torch.empty(1, 2, 4, 5, device="cuda")
+    assert L.pmctf_bilinear_up2_f32(p(xt), p(up), 2, 9, 11, 1.0, None) == 0
+    assert L.pmctf_bilinear_down2_f32(p(xt), p(dn), 2, 9, 11, 1.0, None) == 0
+    torch.cuda.synchronize()
+    assert_same(up.cpu().numpy(), clib.bilinear_up2(x), "pmctf_bilinear_up2_f32")
+    assert_same(dn.cpu().numpy(), clib.bilinear_down2(x), "pmctf_bilinear_down2_f32")
+
+
+def test_grid_stride_kernels_past_the_grid_cap(cuda):
+    """One shape with more work items than the grid cap for the remaining grid-stride kernels: nearest_up2 and
+    pixel_shuffle2 (scalar and 16-byte forms), avgpool2, bilinear_up, bilinear_down, the generic depthwise kernel.
+    (The depthwise strip kernel cannot get there: from 262 144 column threads on, an eighth of the strip threads, the
+    column-walking kernel takes the layer; that one would need operands of 2.1 GB, and is not run past its cap.)"""
+    import torch.nn.functional as F
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    r = _rng(31)
+    for (n, c, h, w) in ((1, 3, 600, 600), (1, 8, 1500, 1400)):                # scalar: 4nhwc items; vec4: nhwc/4
+        assert (4 * n * h * w * c if c % 4 else n * h * w * c // 4) > GRID_CAP
+        x = r.standard_normal((n, c, h, w), dtype=np.float32)
+        assert_same(nchw(ops.nearest_up2(nhwc(x))), F.interpolate(torch.from_numpy(x), scale_factor=2, mode="nearest").numpy(),
+                    f"nearest_up2 {(n, c, h, w)}")
+    for (n, c, h, w) in ((1, 3, 600, 600), (1, 4, 2100, 2000)):
+        assert (4 * n * h * w * c if c % 4 else n * h * w * c // 4) > GRID_CAP
+        x4 = r.standard_normal((n, 4 * c, h, w), dtype=np.float32)
+        want = F.leaky_relu(F.pixel_shuffle(torch.from_numpy(x4), 2), 0.1).numpy()
+        assert_same(nchw(ops.pixel_shuffle2(nhwc(x4), act=ops.ACT_LEAKY, slope=0.1)), want, f"pixel_shuffle2 {(n, c, h, w)}")
+    x = (r.standard_normal((1, 2, 3000, 3001), dtype=np.float32) * 10).astype(np.float32)
+    xt = torch.from_numpy(x).cuda()
+    assert 2 * 1500 * 1500 > GRID_CAP
+    assert_same(ops.avgpool2(xt).cpu().numpy(), clib.avgpool2(x), "avgpool2 past the cap")
+    assert_same(ops.bilinear_down2(xt, 1.0, 2).cpu().numpy(), clib.bilinear_down(x, 2), "bilinear_down past the cap")
+    x = (r.standard_normal((1, 1, 1100, 1000), dtype=np.float32) * 10).astype(np.float32)
+    assert 4 * x.size > GRID_CAP
+    assert_same(ops.bilinear_up2(torch.from_numpy(x).cuda(), 1.0, 2).cpu().numpy(), clib.bilinear_up(x, 2), "bilinear_up past the cap")
+    shape = (1, 6, 900, 800)                                                   # C % 4 != 0: the generic depthwise kernel
+    assert np.prod(shape) > GRID_CAP
+    x = r.standard_normal(shape, dtype=np.float32)
+    w = r.standard_normal((6, 1, 3, 3), dtype=np.float32)
+    b = r.standard_normal(6, dtype=np.float32)
+    assert_same(nchw(ops.DepthwiseConv2d(torch.from_numpy(w), torch.from_numpy(b))(nhwc(x))), clib.dwconv2d(x, w, b),
+                "generic dwconv past the cap")
+
+
+@pytest.mark.parametrize("case", [
+    # N, Cin, H, W, Cout, K, act, rule, work items, cap
+    (1, 4, 540, 500, 8, 3, 2, 0, 540 * 500 * 8, 8192 * 256),          # conv_smallcin_kernel (Cin = 4): one thread per output
+    (1, 2, 600, 500, 16, 3, 0, 1, 600 * 500 // 16, 16384),            # conv_smallcin_reg_kernel: 256 / Cout pixels per workgroup
+    (1, 1, 2100, 2048, 32, 3, 3, 1, 2100 * 32 // 4, 16384),           # strip kernel: four 64-pixel strips per workgroup
+    (1, 16, 2100, 2000, 1, 3, 0, 1, 263 * 63, 16384),                 # few-cout kernel 16 -> 1: one workgroup per 8x32 tile
+    (1, 16, 2100, 2000, 2, 7, 0, 0, 263 * 63, 16384),                 # few-cout kernel 16 -> 2, 7x7
+], ids=["smallcin", "smallcin_reg", "smallcin_strip", "fewcout_16_1", "fewcout_16_2_k7"])
+def test_small_convolutions_past_the_grid_cap(cuda, case):
+    """the vector-ALU convolutions on planes with more workgroups than their grid cap (few-cout: more 8x32 tiles than the
+    other kernels' cap; its LDS form launches one workgroup per tile), against the oracle"""
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    n, cin, h, w, cout, k, act, rule, items, cap = case
+    assert items > cap
+    r = _rng(cin * cout)
+    x = r.standard_normal((n, cin, h, w), dtype=np.float32)
+    wt = (r.standard_normal((cout, cin, k, k), dtype=np.float32) * 0.2).astype(np.float32)
+    b = r.standard_normal(cout, dtype=np.float32)
+    conv = ops.Conv2d(torch.from_numpy(wt), torch.from_numpy(b), 1, (k // 2, k // 2), rule=rule)
+    assert conv.small or conv.few
+    ref = clib.conv2d(x, wt, b, 1, (k // 2, k // 2), rule)
+    if act == 2:
+        ref = np.where(ref > 0, ref, ref * np.float32(0.1)).astype(np.float32)
+    elif act == 3:
+        ref = clib.tanh(ref)
+    assert_same(nchw(conv(nhwc(x), act, 0.1)), ref, f"conv {case}")
+
+
+def test_conv3x3_cin1_dual_past_the_grid_cap(cuda):
+    """PredictUpdate conv1 with its tanh copy on a plane of more than 4.2 M pixels"""
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    r = _rng(41)
+    H, W = 2100, 2001
+    assert H * W > GRID_CAP
+    x = r.standard_normal((1, 1, H, W), dtype=np.float32)
+    wt = (r.standard_normal((16, 1, 3, 3), dtype=np.float32) * 0.3).astype(np.float32)
+    b = r.standard_normal(16, dtype=np.float32)
+    conv = ops.Conv2d(torch.from_numpy(wt), torch.from_numpy(b), 1, (1, 1), rule=1)
+    y, y2 = ops.conv3x3_cin1_dual(conv, nhwc(x), ops.ACT_TANH)
+    ref = clib.conv2d(x, wt, b, 1, (1, 1), 1)
+    assert_same(nchw(y), ref, "conv1")
+    assert_same(nchw(y2), clib.tanh(ref), "tanh(conv1)")
+
+
+def test_lstm_gates_without_aten_tails(cuda):
+    """lstm_gates with aten_threads = 0 (test_lstm_gates_with_aten_thread_tails runs 8): SLEEF's sigmoid on every element,
+    one cell plane broadcast over the channels or one per channel; the last shape is past the grid cap"""
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    rng = _rng(78)
+    for (n, c, h, w, cc) in ((2, 3, 144, 240, 1), (1, 32, 36, 60, 32), (1, 8, 800, 700, 1)):
+        x = (rng.standard_normal((n, c, h, w)) * 3).astype(np.float32)
+        cell = rng.standard_normal((n, cc, h, w)).astype(np.float32)
+        g = clib.sigmoid(x)
+        cn = g * cell + g * clib.tanh(x)
+        hid = g * clib.tanh(np.ascontiguousarray(cn))
+        got_h, got_c = ops.lstm_gates(nhwc(x), nhwc(cell), aten_threads=0)
+        assert_same(nchw(got_h), hid, f"hidden {(n, c, h, w, cc)}")
+        assert_same(nchw(got_c), cn, f"cell {(n, c, h, w, cc)}")
+    assert 8 * 800 * 700 > GRID_CAP
+
+
+@pytest.mark.parametrize("cin", [1, 16], ids=["smallcin", "mfma"])
+def test_relu_epilogue_is_torch_relu_on_nan_and_negative_zero(cuda, cin):
+    """the relu of the convolution epilogues (conv_epilogue.h act_c, pm::apply_act) is torch.relu bit for bit: a NaN stays a
+    NaN and -0 stays -0 (max(0, v) as ATen's CPU kernel takes it).  A 1x1 layer that hands channel 0 through — weight 1 on
+    it, +0 on the others, whose inputs are -0, bias -0, so that every product and the sum of a -0 input are -0 — against
+    torch.relu of the oracle's convolution."""
+    import math_sweep as ms
+    from pmctf_oracle import clib
+    from pMCTF.hip import ops
+    H, W, cout = 8, 16, 16
+    x = np.full((1, cin, H, W), -0.0, np.float32)
+    x[0, 0] = _rng(5).standard_normal((H, W), dtype=np.float32)
+    x[0, 0, 0, :6] = np.array([0x80000000, 0x00000000, 0x7fc00000, 0xffc00001, 0x80000001, 0xff800000], np.uint32).view(np.float32)
+    wt = np.zeros((cout, cin, 1, 1), np.float32)
+    wt[:, 0] = 1.0
+    b = np.full(cout, -0.0, np.float32)
+    conv = ops.Conv2d(torch.from_numpy(wt), torch.from_numpy(b), 1, (0, 0), rule=0)
+    assert conv.small == (cin == 1) and not conv.few
+    pre = clib.conv2d(x, wt, b, 1, (0, 0), 0)
+    assert np.signbit(pre[0, 0, 0, 0]) and pre[0, 0, 0, 0] == 0 and np.isnan(pre[0, :, 0, 2:4]).all()
+    want = torch.relu(torch.from_numpy(pre)).numpy()
+    assert want.view(np.uint32)[0, 0, 0, 0] == 0x80000000 and np.isnan(want[0, :, 0, 2:4]).all()
+    got = np.ascontiguousarray(nchw(conv(nhwc(x), ops.ACT_RELU, 0.0)))
+    count, first, _ = ms.compare(got.reshape(-1), want.reshape(-1))
+    assert count == 0, ms.describe("relu epilogue", np.arange(got.size), got.reshape(-1), want.reshape(-1), count, first)

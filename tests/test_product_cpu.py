@@ -59,6 +59,14 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert L.pmctf_flow_warp_f32(None, None, None, None, None, 1, 1, 8, 8, 1, 1.0, None) == -1
     assert L.pmctf_conv2d_packed_size(112, 112, 3, 3) == 7 * 9 * 7 * 256
     assert L.pmctf_conv2d_packed_bias_size(112) == 112
+    # the diagnostic probe: null or misaligned output, n <= 0 or > 2^32, unknown function — refused before any launch
+    y = 0x1000                                                  # a made-up pointer, passed only with a refused argument
+    assert L.pmctf_math_probe_f32(0, None, 0, 16, None, 0.0, None) == -1
+    assert L.pmctf_math_probe_f32(0, None, 0, 16, y + 4, 0.0, None) == -1
+    for n in (0, -1, (1 << 32) + 1):
+        assert L.pmctf_math_probe_f32(0, None, 0, n, y, 0.0, None) == -1
+    for fn in (-1, 8, 13, 99):                                  # 8 = PMCTF_PROBE_ACT + PMCTF_ACT_NONE: no function
+        assert L.pmctf_math_probe_f32(fn, None, 0, 16, y, 0.0, None) == -1
 
 
 def test_product_path_has_no_cpu_fallback():
