@@ -1599,12 +1599,14 @@ def test_deferred_stage_batching_behind_the_drop_in_api(cuda):
     net.encode_stage_pairs = orig
 
 
-@pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16x2", "bf16"])
 def test_reduced_precision_profile_is_self_consistent(cuda, precision):
     """The AUXILIARY arithmetic profiles (HipEngine(precision=...): the dense 3x3 convolutions on bf16 MFMA with split
     operands) earn no parity claim, but they must be usable: deterministic, decodable by the same build bit for bit
     (decoder in the loop == encoder's reconstruction), close to the exact profile (bits within 1 % / 10 %, PSNR within
-    0.01 / 1 dB), and the exact profile must be untouched by their existence."""
+    0.01 / 1 dB; "bf16x2", the only profile that takes launch_split_wave<7, 2, 1> on the 112-cout layers, is held to the
+    plain-bf16 limits until someone has measured it: the values are printed), and the exact profile must be untouched by
+    their existence."""
     import pmctf_gop
     from pMCTF.hip import ops
     w, h = 448, 256
@@ -1618,7 +1620,7 @@ def test_reduced_precision_profile_is_self_consistent(cuda, precision):
     old = ops.SPLIT_MIN_PX
     ops.SPLIT_MIN_PX = 4096          # small test planes: let the level-0/1 subbands take the split kernel
     try:
-        assert net.engine().precision == precision and net.engine().nsplit == {"bf16x3": 3, "bf16": 1}[precision]
+        assert net.engine().precision == precision and net.engine().nsplit == {"bf16x3": 3, "bf16x2": 2, "bf16": 1}[precision]
         with tempfile.TemporaryDirectory() as td:
             a = pmctf_gop.encode_gop(net, fr, h, w, 3, td)
             files_a = {n: open(os.path.join(td, n), "rb").read() for n in sorted(os.listdir(td))}
