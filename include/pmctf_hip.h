@@ -425,6 +425,30 @@ int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, const float 
                             int h, int w, int msssim, float *scratch, double *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Pictures in and out (csrc/picture_ops.hip).  One launch each, no synchronisation.  h, w even, positive and at most
+ * 16384; PMCTF_EINVAL otherwise, and for a null pointer, before anything is launched.
+ *
+ * pmctf_yuv420_to_rgb8_f32: the decoded picture the harness saves as a PNG (test_pMCTF_flex.py:76-79,301-317,334-336).
+ *   rec_y (1,1,Hp,Wp), rec_c (2,1,Hp/2,Wp/2) as for pmctf_frame_quality_f32 (padded, neither clamped nor rounded) ->
+ *   rgb: h*w*3 bytes, [h][w][3] interleaved R,G,B (4-byte aligned).  Per pixel, in the order of the quality front end:
+ *   rint(clamp(.)) of luma and of the four chroma taps, x2 bilinear (align_corners=False), ycbcr2rgb, rint, then the
+ *   clamp(., 0, 255) and cast of save_torch_image.  Hp >= h, Wp >= w, both even.
+ * pmctf_yuv420_u8_to_planes_f32: one picture as it lies in a planar 8-bit 4:2:0 file (h*w luma bytes, then two planes of
+ *   (h/2)*(w/2)) -> the model's inputs (test_pMCTF_flex.py:151-192): y_pad (1,1,Hp,Wp) and c_pad (2,1,Hp/2,Wp/2), the
+ *   bytes as float32, zero outside the picture (the kernel writes the padding itself; 16-byte aligned), and, unless
+ *   null, the un-padded y_org (1,1,h,w) and c_org (2,1,h/2,w/2).  The counterpart of pmctf_planes_to_u8.
+ * pmctf_rgb8_to_yuv420_u8: rgb [h][w][3] bytes -> one picture in the file layout above.  rgb2ycbcr
+ *   (pMCTF/utils/util.py:21-40, as the data path applies it, pMCTF/datasets/video.py:146) in float32 in its written order:
+ *   y = (0.299 R + 0.587 G) + 0.114 B, cb = (B - y) 0.564 + 128, cr = (R - y) 0.713 + 128 on the unrounded y; the Y byte
+ *   is rint(clamp(y, 0, 255)), a chroma byte rint(clamp((((c00 + c01) + c10) + c11) * 0.25, 0, 255)) of the unrounded
+ *   values of its 2x2 block (upper pair first), ties to even. */
+int pmctf_yuv420_to_rgb8_f32(const float *rec_y, const float *rec_c, uint8_t *rgb, int Hp, int Wp, int h, int w,
+                             void *stream);
+int pmctf_yuv420_u8_to_planes_f32(const uint8_t *src, float *y_pad, float *c_pad, float *y_org, float *c_org, int Hp, int Wp,
+                                  int h, int w, void *stream);
+int pmctf_rgb8_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int h, int w, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * DIAGNOSTIC entry point; the codec never calls it.  Evaluates one of the scalar functions behind every kernel above
  * (csrc/pm_device_math.h, pm_sleef_f32.h, pm_glibc_expf.h) on n float32 bit patterns, as the GPU compiler built them:
  * y[i] = fn(bits[i]), or fn(first_bits + i) (mod 2^32) when bits == NULL, so that all 2^32 inputs can be swept without

@@ -15,6 +15,7 @@
 
 #include "../../include/pmctf_hip.h"
 #include "launch.h"
+#include "picture_math.h"
 
 #define Q_THREADS 256
 #define Q_FRONT_BLOCKS 1024                      // partial sums of the front end: [Q_FRONT_BLOCKS][4] doubles
@@ -46,31 +47,6 @@ __device__ __forceinline__ T block_sum(T v, T *buf) {
     T s = buf[0];
     for (int i = 1; i < Q_THREADS / 64; ++i) s += buf[i];
     return s;
-}
-
-__device__ __forceinline__ float round_u8(float v) { return rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
-
-// x2 bilinear, align_corners=False, of a plane of integers: output sample o takes input samples i0, i1 with weights
-// w0, 1 - w0 (0.25 / 0.75, clamped at the edges).  Exact in float32 for integer inputs <= 255.
-__device__ __forceinline__ void up2_taps(int o, int n, int &i0, int &i1, float &w0) {
-    const int k = o >> 1;
-    if (o & 1) {
-        i0 = k;
-        i1 = min(k + 1, n - 1);
-        w0 = 0.75f;
-    } else {
-        i0 = max(k - 1, 0);
-        i1 = k;
-        w0 = 0.25f;
-    }
-}
-
-// pMCTF/utils/util.py:ycbcr2rgb followed by round, in the written order
-__device__ __forceinline__ void to_rgb(float y, float cb, float cr, float &r, float &g, float &b) {
-    const float dcb = cb - 128.0f, dcr = cr - 128.0f;
-    r = rintf(y + 1.403f * dcr);
-    g = rintf((y - 0.714f * dcr) - 0.344f * dcb);
-    b = rintf(y + 1.773f * dcb);
 }
 
 __global__ __launch_bounds__(Q_THREADS) void quality_front_kernel(

@@ -585,6 +585,89 @@ def frame_quality(rec_y, rec_c, org_y, org_c, h, w, msssim=True, return_means=Fa
 
 
 # ------------------------------------------------------------------------------------------------
+# pictures in and out (csrc/picture_ops.hip)
+PICTURE_MAX_SIDE = 16384
+
+
+def _pu8(t):
+    if t is None:
+        return None
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), "expect dense uint8 device tensor"
+    return C.c_void_p(t.data_ptr())
+
+
+def _picture_size(h, w):
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or (h | w) & 1 or max(h, w) > PICTURE_MAX_SIDE:
+        raise ValueError(f"4:2:0 pictures have even, positive sizes up to {PICTURE_MAX_SIDE} (got {h}x{w})")
+    return h, w
+
+
+def frame_to_rgb8(rec_y, rec_c, h, w):
+    """One reconstructed frame as the harness saves it (test_pMCTF_flex.py:76-79,301-317): rec_y (1,1,Hp,Wp) / rec_c
+    (2,1,Hp/2,Wp/2) padded float32, neither clamped nor rounded -> (h, w, 3) uint8 device tensor, the rounded RGB picture
+    of frame_quality clipped to 0..255.  One launch."""
+    h, w = _picture_size(h, w)
+    for t in (rec_y, rec_c):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("expect float32 tensors")
+    rec_y, rec_c = rec_y.contiguous(), rec_c.contiguous()
+    Hp, Wp = rec_y.shape[-2:]
+    if (Hp | Wp) & 1 or h > Hp or w > Wp:
+        raise ValueError(f"picture size {h}x{w} must lie inside the even padded size {Hp}x{Wp}")
+    if rec_y.numel() != Hp * Wp or tuple(rec_c.shape) != (2, 1, Hp // 2, Wp // 2):
+        raise ValueError("expect a luma (1,1,Hp,Wp) and a chroma (2,1,Hp/2,Wp/2) reconstruction")
+    _dev(rec_y), _dev(rec_c)
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=rec_y.device)
+    _lib.check(_lib.hip().pmctf_yuv420_to_rgb8_f32(_p(rec_y), _p(rec_c), _pu8(out), Hp, Wp, h, w, _stream()), "frame_to_rgb8")
+    return out
+
+
+def planes_from_u8(frame_u8, h, w, psize=128, originals=True):
+    """One picture as it lies in a planar 8-bit 4:2:0 file (uint8 device tensor of h*w*3/2 bytes) -> (y_pad (1,1,Hp,Wp),
+    c_pad (2,1,Hp/2,Wp/2), y_org (1,1,h,w), c_org (2,1,h/2,w/2)) float32: the model's inputs, zero padded right / bottom to
+    multiples of psize, and the un-padded originals (None, None with originals=False).  One launch; the counterpart of
+    planes_to_u8."""
+    from ..utils.stream_helper import get_padding_size
+    h, w = _picture_size(h, w)
+    psize = int(psize)
+    if psize <= 0 or psize & 1:
+        raise ValueError(f"psize must be even and positive (got {psize})")
+    if not isinstance(frame_u8, torch.Tensor) or frame_u8.dtype != torch.uint8:
+        raise ValueError("expect a uint8 tensor")
+    if frame_u8.numel() != h * w * 3 // 2:
+        raise ValueError(f"a {h}x{w} 4:2:0 picture has {h * w * 3 // 2} bytes, got {frame_u8.numel()}")
+    dev = _dev(frame_u8)
+    frame_u8 = frame_u8.contiguous()
+    _, right, _, bottom = get_padding_size(h, w, p=psize)
+    Hp, Wp = h + bottom, w + right
+    if max(Hp, Wp) > PICTURE_MAX_SIDE:
+        raise ValueError(f"padded size {Hp}x{Wp} exceeds {PICTURE_MAX_SIDE}")
+    y_pad = torch.empty((1, 1, Hp, Wp), dtype=torch.float32, device=dev)
+    c_pad = torch.empty((2, 1, Hp // 2, Wp // 2), dtype=torch.float32, device=dev)
+    y_org = torch.empty((1, 1, h, w), dtype=torch.float32, device=dev) if originals else None
+    c_org = torch.empty((2, 1, h // 2, w // 2), dtype=torch.float32, device=dev) if originals else None
+    _lib.check(_lib.hip().pmctf_yuv420_u8_to_planes_f32(_pu8(frame_u8), _p(y_pad), _p(c_pad), _p(y_org), _p(c_org), Hp, Wp,
+                                                        h, w, _stream()), "planes_from_u8")
+    return y_pad, c_pad, y_org, c_org
+
+
+def rgb8_to_yuv420(rgb_u8):
+    """(h, w, 3) uint8 RGB device tensor -> uint8 device tensor of h*w*3/2 bytes, one planar 4:2:0 picture in the file
+    layout: rgb2ycbcr (pMCTF/utils/util.py:21-40) in float32, 2x2 mean of the unrounded chroma, round half to even."""
+    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.dtype != torch.uint8:
+        raise ValueError("expect a uint8 tensor")
+    if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3:
+        raise ValueError(f"expect an (h, w, 3) picture, got {tuple(rgb_u8.shape)}")
+    h, w = _picture_size(rgb_u8.shape[0], rgb_u8.shape[1])
+    dev = _dev(rgb_u8)
+    rgb_u8 = rgb_u8.contiguous()
+    out = torch.empty(h * w * 3 // 2, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.hip().pmctf_rgb8_to_yuv420_u8(_pu8(rgb_u8), _pu8(out), h, w, _stream()), "rgb8_to_yuv420")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # diagnostic (csrc/math_probe.hip): the device's scalar functions on raw float32 bit patterns; never on the codec's path
 PROBE_TANH, PROBE_TANH_LDS, PROBE_SIGMOID, PROBE_SIGMOID_SCALAR, PROBE_LOG, PROBE_LOG_POLY, PROBE_EXP, \
     PROBE_GLIBC_EXP, PROBE_ACT = range(9)                    # PMCTF_PROBE_* of include/pmctf_hip.h; PROBE_ACT + ACT_*

@@ -261,6 +261,107 @@ def read_gop(reader, gop, device, psize=128):
     return padded, orig, size
 
 
+class PNGReader:
+    """A sequence of PNG pictures with the YUVReader interface used here (read_one_frame, close, width, height), for
+    sources that are not .yuv files.  paths_or_folder: a list of paths, taken in the given order, or a folder, meaning its
+    *.png in natural numeric order (2.png before 10.png), then by name.  Pictures are opened as
+    Image.open(p).convert("RGB") (read_image_to_torch, test_pMCTF_flex.py:62-67) and returned as (h, w, 3) uint8 RGB
+    arrays: the conversion to 4:2:0 happens on the device (read_gop_device, pngs_to_yuv).  Every picture must have the size
+    of the first (AssertionError, as in read_gop), and that size must be even (ValueError)."""
+
+    def __init__(self, paths_or_folder):
+        import re
+        if isinstance(paths_or_folder, (str, os.PathLike)):
+            folder = os.fspath(paths_or_folder)
+            if not os.path.isdir(folder):
+                raise AssertionError(f"no such folder of pictures: {folder}")
+            names = [n for n in os.listdir(folder) if n.lower().endswith(".png")]
+            # runs of digits compare as numbers (and before text at the same place), the rest as lower-case text
+            names.sort(key=lambda n: ([(0, int(t), "") if t.isdigit() else (1, 0, t.lower())
+                                       for t in re.split(r"(\d+)", n) if t], n))
+            self.paths = [os.path.join(folder, n) for n in names]
+        else:
+            self.paths = [os.fspath(p) for p in paths_or_folder]
+        if not self.paths:
+            raise AssertionError(f"no PNG pictures in {paths_or_folder}")
+        self.current_frame_index = 0
+        self.eof = False
+        first = self._open(self.paths[0])
+        self.height, self.width = int(first.shape[0]), int(first.shape[1])
+        if (self.width | self.height) & 1:
+            raise ValueError(f"{self.paths[0]}: 4:2:0 coding needs an even picture size, got {self.width}x{self.height}")
+
+    @staticmethod
+    def _open(path):
+        import numpy as np
+        from PIL import Image
+        with Image.open(path) as im:
+            return np.array(im.convert("RGB"), dtype=np.uint8)          # a copy the caller owns: (h, w, 3), C order
+
+    def __len__(self):
+        return len(self.paths)
+
+    def read_one_frame(self):
+        """-> (h, w, 3) uint8 RGB array of the next picture, None past the end"""
+        if self.current_frame_index >= len(self.paths):
+            self.eof = True
+            return None
+        path = self.paths[self.current_frame_index]
+        rgb = self._open(path)
+        assert rgb.shape == (self.height, self.width, 3), f"picture size changes inside the sequence ({path})"
+        self.current_frame_index += 1
+        return rgb
+
+    def close(self):
+        self.current_frame_index = 0
+        self.eof = False
+
+
+def _need_gpu(device, what):
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"{what} runs on the GPU (no CPU fallback)")
+
+
+def read_gop_device(reader, gop, device, psize=128):
+    """read_gop with the arithmetic on the device: the same triple, tensor for tensor and bit for bit.  From a YUVReader a
+    picture costs one copy of its bytes to the device and one launch (pmctf_yuv420_u8_to_planes_f32: conversion, padding
+    and the un-padded originals); from a PNGReader the RGB bytes are copied and converted to 4:2:0 first
+    (pmctf_rgb8_to_yuv420_u8)."""
+    import numpy as np
+    from pMCTF.hip import ops
+    _need_gpu(device, "read_gop_device")
+    padded, orig, size = [], [], None
+    for _ in range(gop):
+        pic = reader.read_one_frame()
+        assert pic is not None, "sequence ends inside a GOP"
+        if isinstance(pic, np.ndarray):                                 # RGB picture of a PNGReader
+            shape = tuple(pic.shape[:2])
+            frame = ops.rgb8_to_yuv420(torch.from_numpy(pic).to(device))
+        else:
+            shape = tuple(pic[0].shape)
+            frame = torch.from_numpy(np.concatenate([p.reshape(-1) for p in pic])).to(device)
+        assert size in (None, shape), "picture size changes inside the sequence"
+        size = shape
+        y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, size[0], size[1], psize=psize)
+        orig.append([y_org, c_org])
+        padded.append([y_pad, c_pad])
+    return padded, orig, size
+
+
+def pngs_to_yuv(paths_or_folder, yuv_out, device):
+    """A PNG sequence (see PNGReader) -> planar 8-bit 4:2:0 file, converted on the device (pmctf_rgb8_to_yuv420_u8): the
+    .yuv that codes to the same files as the PNGs themselves.  -> (width, height, frames)"""
+    from pMCTF.hip import ops
+    _need_gpu(device, "pngs_to_yuv")
+    reader = PNGReader(paths_or_folder)
+    with open(yuv_out, "wb") as f:
+        for _ in range(len(reader)):
+            frame = ops.rgb8_to_yuv420(torch.from_numpy(reader.read_one_frame()).to(device))
+            f.write(frame.cpu().numpy().tobytes(order="C"))
+    reader.close()
+    return reader.width, reader.height, len(reader)
+
+
 def rgb_psnr(rec_y, rec_c, y, c):
     """PSNR of the rounded RGB pictures (chroma bilinearly up-sampled), test_pMCTF_flex.py:312-321"""
     from pMCTF.utils.util import ycbcr2rgb, yuv_420_to_444
@@ -269,7 +370,8 @@ def rgb_psnr(rec_y, rec_c, y, c):
 
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                    skip_decoding=True, psize=128, keep_gops=False, msssim=False):
+                    skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
+                    keep_gops=False, msssim=False):
     """What the evaluation harness produces for one sequence (test_pMCTF_flex.py:run_test, 86-346) built from this
     module's own pieces: pictures come from a planar .yuv through YUVReader and get_padding_size, every closed GOP goes
     through encode_gop (one encode_one_stage call per pair, both per-pair report lines), decode_gop and gop_psnr, and
@@ -280,13 +382,31 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     (0 is reported, as by the harness, when a side is 128 or less).
     keep_gops=True: GOP k goes to bin_folder/gop_{k:05d}/ instead of overwriting GOP k-1's files, and bin_folder gets the
     sequence.json header decode_sequence needs (write_sequence_header).
+    src_format="png": yuv_path is a folder of PNGs or a list of paths (PNGReader); width and height are checked against
+    the files; the pictures are converted to 4:2:0 and padded on the device (read_gop_device).
+    ingest="device": a .yuv source goes through read_gop_device as well (bytes to the device, one launch per picture)
+    instead of read_gop's host conversion; the tensors are the same bit for bit.  Either needs a GPU (RuntimeError).
+    decoded_frame_path: a folder that receives every reconstructed frame as {frame index}.png, the harness's
+    --save_decoded_frame (test_pMCTF_flex.py:334-336), through frames_to_rgb8; nothing is added to bin_folder.
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
     import io
     import time
     from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
     from pMCTF.utils.yuv_reader import YUVReader
     assert frame_num % gop == 0
-    reader = YUVReader(yuv_path, width, height, start_index=0)
+    if src_format not in ("yuv", "png") or ingest not in ("host", "device"):
+        raise ValueError(f"src_format is 'yuv' or 'png' and ingest 'host' or 'device' (got {src_format!r}, {ingest!r})")
+    on_device = src_format == "png" or ingest == "device"
+    if on_device:
+        _need_gpu(device, f"encode_sequence(src_format={src_format!r}, ingest={ingest!r})")
+    if src_format == "png":
+        reader = PNGReader(yuv_path)
+        if (reader.width, reader.height) != (width, height):
+            raise ValueError(f"the pictures are {reader.width}x{reader.height}, not {width}x{height}")
+        if len(reader) < frame_num:
+            raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
+    else:
+        reader = YUVReader(yuv_path, width, height, start_index=0)
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines = []
     ssims = []
@@ -295,7 +415,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     t0 = time.time()
     with torch.no_grad():
         for k in range(frame_num // gop):
-            padded, orig, (h, w) = read_gop(reader, gop, device, psize)
+            padded, orig, (h, w) = (read_gop_device if on_device else read_gop)(reader, gop, device, psize)
+            first_frame = k * gop
             folder = bin_folder
             if keep_gops:
                 folder = os.path.join(bin_folder, gop_folder(k))
@@ -307,6 +428,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                     seconds[k] += r[k]
             lines += enc["log"]
             rec = decode_gop(codec, enc["frames_coded"])
+            if decoded_frame_path is not None:
+                write_pngs(decoded_frame_path, first_frame, frames_to_rgb8(rec, h, w))
             quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
             tables["bits"] += enc["bits"]
             tables["bpp_mv"] += [b / (h * w) for b in enc["bits_mv"]]
@@ -572,12 +695,40 @@ def frames_to_u8(frames_rec, pic_height, pic_width):
     return [(y[0], c[0], c[1]) for y, c in host]
 
 
-def decode_sequence(codec, bin_folder, yuv_out, device=None):
+def frames_to_rgb8(frames_rec, pic_height, pic_width):
+    """reconstructed (padded, float) pictures -> [(h, w, 3) uint8 RGB arrays] of the un-padded size, the pictures the
+    harness saves (test_pMCTF_flex.py:76-79,313-317): one launch (pmctf_yuv420_to_rgb8_f32) and one copy of bytes to the
+    host per picture.  The sibling of frames_to_u8."""
+    from pMCTF.hip import ops
+    out = [ops.frame_to_rgb8(rec[0].float(), rec[1].float(), pic_height, pic_width) for rec in frames_rec]
+    return [rgb.cpu().numpy() for rgb in out]
+
+
+def write_pngs(folder, first_index, pictures):
+    """[(h, w, 3) uint8 RGB arrays] -> folder/{first_index}.png, {first_index + 1}.png, ...: the harness's naming
+    (test_pMCTF_flex.py:335).  -> the paths written"""
+    from PIL import Image
+    os.makedirs(folder, exist_ok=True)
+    paths = []
+    for i, rgb in enumerate(pictures):
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or str(rgb.dtype) != "uint8":
+            raise ValueError(f"expect (h, w, 3) uint8 pictures, got {rgb.shape} {rgb.dtype}")
+        paths.append(os.path.join(folder, f"{first_index + i}.png"))
+        Image.fromarray(rgb).save(paths[-1])
+    return paths
+
+
+def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
     """Decode a folder written by encode_sequence(keep_gops=True) into a planar 8-bit 4:2:0 file (the layout YUVReader
     reads), GOP by GOP.  The codec holds the weights the sequence was coded with; its number of motion stages, arithmetic
     profile and ATen thread setting must equal the header's (ValueError otherwise).  device: checked against the
-    codec's, if given.  Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP}."""
+    codec's, if given.  png_out: a folder that receives every decoded picture as {index}.png (frames_to_rgb8, write_pngs);
+    yuv_out may then be None (PNGs only).
+    Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP}."""
+    import contextlib
     import time
+    if yuv_out is None and png_out is None:
+        raise ValueError("nothing to write: give yuv_out, png_out or both")
     header = read_sequence_header(bin_folder)
     check_sequence_header(header, codec_header_fields(codec))
     dev = codec.engine().dev
@@ -585,15 +736,18 @@ def decode_sequence(codec, bin_folder, yuv_out, device=None):
         raise ValueError(f"the codec lives on {dev}, not on {device}")
     h, w = header["height"], header["width"]
     shapes, seconds = [], []
-    with open(yuv_out, "wb") as f:
+    with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
         for k in range(header["frame_num"] // header["gop"]):
             t0 = time.time()
             out = decode_gop_files(codec, os.path.join(bin_folder, gop_folder(k)), header["gop"], h, w, header["q_index"],
                                    psize=header["psize"], me_downsample=header["me_downsample"],
                                    ll_order=header["ll_order"])
-            for planes in frames_to_u8(out["frames"], h, w):
-                for p in planes:
-                    f.write(p.tobytes(order="C"))
-                shapes.append((h, w))
+            if f is not None:
+                for planes in frames_to_u8(out["frames"], h, w):
+                    for p in planes:
+                        f.write(p.tobytes(order="C"))
+            if png_out is not None:
+                write_pngs(png_out, k * header["gop"], frames_to_rgb8(out["frames"], h, w))
+            shapes += [(h, w)] * header["gop"]
             seconds.append(time.time() - t0)
     return {"header": header, "frames": shapes, "seconds": seconds}

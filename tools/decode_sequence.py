@@ -3,6 +3,7 @@
 
     python tools/decode_sequence.py --checkpoint model.pth BIN_FOLDER OUT.yuv
     python tools/decode_sequence.py --synth-seed 0 BIN_FOLDER OUT.yuv        (the deterministic synthetic weights)
+    python tools/decode_sequence.py --synth-seed 0 --png DIR BIN_FOLDER      (RGB pictures DIR/{index}.png; OUT.yuv optional)
 
 The number of motion stages comes from the folder's sequence.json; the weights must be the ones the sequence was coded
 with.  The decoder refuses a header whose arithmetic profile (PMCTF_PRECISION) or ATen thread setting
@@ -22,9 +23,12 @@ def main():
     w.add_argument("--checkpoint", help="weights file (torch.save of a state_dict, or of a dict holding one)")
     w.add_argument("--synth-seed", type=int, help="deterministic synthetic weights (pmctf_synth) with this seed")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--png", metavar="DIR", help="also write every decoded picture there as {index}.png (RGB)")
     ap.add_argument("bin_folder")
-    ap.add_argument("yuv_out")
+    ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args()
+    if a.yuv_out is None and a.png is None:
+        ap.error("give OUT.yuv, --png DIR or both")
     import torch
     import pmctf_gop
     from pMCTF.models.video.pMCTF_L import pMCTF
@@ -39,9 +43,9 @@ def main():
     net = net.to(a.device)
     net.update(force=True)
     with torch.no_grad():
-        out = pmctf_gop.decode_sequence(net, a.bin_folder, a.yuv_out, a.device)
+        out = pmctf_gop.decode_sequence(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png)
     n = len(out["frames"])
-    print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out,
+    print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out, "png": a.png,
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9)}))
 
 

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Code a sequence into a folder of bitstream files (pmctf_gop.encode_sequence(keep_gops=True)) and print the harness's
+JSON record.
+
+    python tools/encode_sequence.py --checkpoint model.pth --width 1920 --height 1080 SOURCE.yuv BIN_FOLDER
+    python tools/encode_sequence.py --synth-seed 0 PNG_FOLDER BIN_FOLDER      (the deterministic synthetic weights)
+
+SOURCE is a planar 8-bit 4:2:0 file (--width and --height required) or a folder of PNG pictures, taken in natural numeric
+order and converted to 4:2:0 on the GPU (their size is read from the files).  tools/decode_sequence.py reads BIN_FOLDER
+back with the same weights."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "learned-pmctf_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    w = ap.add_mutually_exclusive_group(required=True)
+    w.add_argument("--checkpoint", help="weights file (torch.save of a state_dict, or of a dict holding one)")
+    w.add_argument("--synth-seed", type=int, help="deterministic synthetic weights (pmctf_synth) with this seed")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--num-me-stages", type=int, default=1, help="number of motion-estimation networks of the weights")
+    ap.add_argument("--gop", type=int, default=8, help="GOP length, a power of two")
+    ap.add_argument("--q-index", type=int, default=3)
+    ap.add_argument("--frames", type=int, help="pictures to code (default: all whole GOPs of the source)")
+    ap.add_argument("--width", type=int, help="picture width (.yuv sources)")
+    ap.add_argument("--height", type=int, help="picture height (.yuv sources)")
+    ap.add_argument("--decoded-frames", metavar="DIR", help="save every reconstructed frame there as {index}.png")
+    ap.add_argument("--msssim", action="store_true", help="fill the MS-SSIM fields of the record (GPU quality kernels)")
+    ap.add_argument("source", help=".yuv file or folder of PNGs")
+    ap.add_argument("bin_folder")
+    a = ap.parse_args()
+    import torch
+    import pmctf_gop
+    from pMCTF.models.video.pMCTF_L import pMCTF
+    try:
+        pmctf_gop.gop_pairs(a.gop)
+    except ValueError as e:
+        ap.error(str(e))
+    if os.path.isdir(a.source):
+        src_format, reader = "png", pmctf_gop.PNGReader(a.source)
+        width, height, available = reader.width, reader.height, len(reader)
+        if (a.width, a.height) not in ((None, None), (width, height)):
+            ap.error(f"the pictures are {width}x{height}, not {a.width}x{a.height}")
+    else:
+        if a.width is None or a.height is None:
+            ap.error("--width and --height are required for a .yuv source")
+        src_format, width, height = "yuv", a.width, a.height
+        available = os.path.getsize(a.source) // (width * height + 2 * (width // 2) * (height // 2))
+    frames = a.frames if a.frames is not None else available // a.gop * a.gop
+    if frames <= 0 or frames % a.gop or frames > available:
+        ap.error(f"{frames} frames: need a positive multiple of the GOP length {a.gop}, at most the {available} of the source")
+    net = pMCTF(num_me_stages=a.num_me_stages).eval()
+    if a.checkpoint is not None:
+        from pMCTF.utils.stream_helper import get_state_dict
+        net.load_state_dict(get_state_dict(a.checkpoint), strict=True)
+    else:
+        import pmctf_synth
+        net.load_state_dict(pmctf_synth.synth_state_dict(net.state_dict(), seed=a.synth_seed), strict=True)
+    net = net.to(a.device)
+    net.update(force=True)
+    os.makedirs(a.bin_folder, exist_ok=True)
+    with torch.no_grad():
+        out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+                                        src_format=src_format, decoded_frame_path=a.decoded_frames, keep_gops=True,
+                                        msssim=a.msssim)
+    print(out["json"])
+
+
+if __name__ == "__main__":
+    main()
