@@ -449,6 +449,26 @@ int pmctf_yuv420_u8_to_planes_f32(const uint8_t *src, float *y_pad, float *c_pad
 int pmctf_rgb8_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int h, int w, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Picture hashes (csrc/picture_hash.hip): crc_out[s] = CRC-32 of the bytes [data, data + bytes) of segs[s], s < n_segs, as
+ * zlib.crc32 computes it (reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF).  The encoder records
+ * the hashes of its reconstructed pictures, the decoder recomputes and compares them (pmctf_gop.picture_hashes).
+ *   segs: the table of ranges, in DEVICE memory like the ranges themselves, 8-byte aligned.  A range may start at any byte
+ *   address (plane 1 of a cropped 4:2:0 chroma tensor starts at an odd one for some sizes); bytes == 0 gives 0 and its
+ *   data is not looked at.  crc_out: n_segs values on the device, 4-byte aligned; nothing around them is written.
+ *   slices: workgroups per range, 1..1024, a launch shape only (0: 64); a range's 16-byte pieces are dealt to them in
+ *   spans of whole tiles of PMCTF_CRC32_TILE_BYTES.  Results do not depend on it.
+ * Two launches whatever n_segs and the lengths are, no memset, no synchronisation.  Partial remainders are combined with
+ * integer XOR atomics, which do not depend on the order of arrival: the same input gives the same bits on every run.
+ * n_segs == 0 launches nothing.  PMCTF_EINVAL, before any launch, for a null or misaligned table or output, n_segs < 0
+ * or > 65535, slices out of range. */
+#define PMCTF_CRC32_TILE_BYTES 4096
+typedef struct pmctf_crc_segment {
+    const void *data;
+    uint64_t bytes;
+} pmctf_crc_segment;                    /* 16 bytes */
+int pmctf_crc32_segments(const pmctf_crc_segment *segs, int n_segs, int slices, uint32_t *crc_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * DIAGNOSTIC entry point; the codec never calls it.  Evaluates one of the scalar functions behind every kernel above
  * (csrc/pm_device_math.h, pm_sleef_f32.h, pm_glibc_expf.h) on n float32 bit patterns, as the GPU compiler built them:
  * y[i] = fn(bits[i]), or fn(first_bits + i) (mod 2^32) when bits == NULL, so that all 2^32 inputs can be swept without

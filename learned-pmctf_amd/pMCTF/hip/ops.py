@@ -667,6 +667,49 @@ def rgb8_to_yuv420(rgb_u8):
     return out
 
 
+CRC32_TILE_BYTES = 4096                    # PMCTF_CRC32_TILE_BYTES of include/pmctf_hip.h
+CRC32_MAX_SEGMENTS = 65535
+
+
+def crc32(tensors, slices=None, out=None):
+    """zlib.crc32 of the bytes of every tensor of a list, as stored (any dtype, any start address), taken on the device
+    (pmctf_crc32_segments): ONE call into the library for the whole list and one device->host copy of 4 bytes per tensor.
+    -> [int].  An empty tensor gives 0.  ValueError for a tensor that is not contiguous or not on the device.
+    slices: workgroups per tensor (a launch shape, results do not depend on it); by default from the longest tensor, eight
+    tiles of CRC32_TILE_BYTES per workgroup, at most 128.  out: an int32 device tensor that receives the values (one per
+    tensor; by default a new one)."""
+    tensors = list(tensors)
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("crc32 hashes device tensors (there is no CPU path: use zlib.crc32 for bytes on the host)")
+        if not t.is_contiguous():
+            raise ValueError(f"crc32 hashes the bytes as stored: a tensor of shape {tuple(t.shape)} and strides "
+                             f"{tuple(t.stride())} is not contiguous")
+    S = len(tensors)
+    if S == 0:
+        return []
+    if S > CRC32_MAX_SEGMENTS:
+        raise ValueError(f"at most {CRC32_MAX_SEGMENTS} tensors per call (got {S})")
+    dev = _dev(tensors[0])
+    if any(t.device != dev for t in tensors):
+        raise ValueError("crc32: the tensors of one call live on one device")
+    lengths = [t.numel() * t.element_size() for t in tensors]
+    table = []
+    for t, n in zip(tensors, lengths):
+        table += [t.data_ptr() if n else 0, n]
+    segs = torch.tensor(table, dtype=torch.int64).to(dev)                   # pmctf_crc_segment[S]
+    if slices is None:
+        slices = max(1, min(128, -(-max(lengths) // (8 * CRC32_TILE_BYTES))))
+    if out is None:
+        out = torch.empty(S, dtype=torch.int32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
+              and out.numel() == S):
+        raise ValueError(f"out: a contiguous int32 device tensor of {S} values")
+    _lib.check(_lib.hip().pmctf_crc32_segments(C.c_void_p(segs.data_ptr()), S, int(slices), C.c_void_p(out.data_ptr()),
+                                               _stream()), "crc32")
+    return [v & 0xffffffff for v in out.cpu().tolist()]
+
+
 # ------------------------------------------------------------------------------------------------
 # diagnostic (csrc/math_probe.hip): the device's scalar functions on raw float32 bit patterns; never on the codec's path
 PROBE_TANH, PROBE_TANH_LDS, PROBE_SIGMOID, PROBE_SIGMOID_SCALAR, PROBE_LOG, PROBE_LOG_POLY, PROBE_EXP, \

@@ -371,7 +371,7 @@ def rgb_psnr(rec_y, rec_c, y, c):
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
                     skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
-                    keep_gops=False, msssim=False):
+                    picture_hash=None, keep_gops=False, msssim=False):
     """What the evaluation harness produces for one sequence (test_pMCTF_flex.py:run_test, 86-346) built from this
     module's own pieces: pictures come from a planar .yuv through YUVReader and get_padding_size, every closed GOP goes
     through encode_gop (one encode_one_stage call per pair, both per-pair report lines), decode_gop and gop_psnr, and
@@ -388,9 +388,16 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     instead of read_gop's host conversion; the tensors are the same bit for bit.  Either needs a GPU (RuntimeError).
     decoded_frame_path: a folder that receives every reconstructed frame as {frame index}.png, the harness's
     --save_decoded_frame (test_pMCTF_flex.py:334-336), through frames_to_rgb8; nothing is added to bin_folder.
+    picture_hash="u8" or "f32" (needs keep_gops=True; default None: off, no file): the CRC-32 of every reconstructed picture,
+    taken on the device (picture_hashes), goes to bin_folder/picture_hashes.json, where decode_sequence finds and checks
+    it; the result gains "picture_hashes".  sequence.json is the same either way.
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
     import io
     import time
+    if picture_hash is not None and picture_hash not in HASH_LEVELS:
+        raise ValueError(f"picture_hash is None or one of {HASH_LEVELS} (got {picture_hash!r})")
+    if picture_hash is not None and not keep_gops:
+        raise ValueError("picture_hash needs keep_gops=True: the hashes belong to a folder decode_sequence can read")
     from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
     from pMCTF.utils.yuv_reader import YUVReader
     assert frame_num % gop == 0
@@ -410,6 +417,7 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines = []
     ssims = []
+    hashes = []
     pairs = 0
     seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
     t0 = time.time()
@@ -428,6 +436,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                     seconds[k] += r[k]
             lines += enc["log"]
             rec = decode_gop(codec, enc["frames_coded"])
+            if picture_hash is not None:
+                hashes += picture_hashes(rec, h, w, picture_hash)
             if decoded_frame_path is not None:
                 write_pngs(decoded_frame_path, first_frame, frames_to_rgb8(rec, h, w))
             quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
@@ -448,6 +458,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
         write_sequence_header(bin_folder, width=width, height=height, frame_num=frame_num, gop=gop, q_index=q_index,
                               psize=psize, me_downsample=1, ll_order="plane" if skip_decoding else "position",
                               **codec_header_fields(codec))
+        if picture_hash is not None:
+            write_picture_hashes(bin_folder, picture_hash, hashes)
     for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
         lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
     record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
@@ -457,6 +469,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     out = dict(tables, log=record, json=text.getvalue(), lines=lines)
     if msssim:
         out["msssim"] = ssims
+    if picture_hash is not None:
+        out["picture_hashes"] = hashes
     return out
 
 
@@ -718,15 +732,192 @@ def write_pngs(folder, first_index, pictures):
     return paths
 
 
+# ------------------------------------------------------------------------------------------------------- picture hashes
+# The encoder records the CRC-32 (zlib.crc32) of every reconstructed picture, the decoder recomputes and compares: the
+# check that the decoder reproduces the encoder's reconstruction, on the user's own sequence.  A frame's "frame" value is
+# the CRC-32 of that frame's bytes in the decoded .yuv, so a decoded file can be checked with zlib alone
+# (check_yuv_hashes, tools/check_picture_hashes.py).
+PICTURE_HASHES = "picture_hashes.json"
+PICTURE_HASH_FORMAT_VERSION = 1
+HASH_LEVELS = ("u8", "f32")
+HASH_KEYS = {"u8": ("y", "cb", "cr", "frame"), "f32": ("y", "cb", "cr", "frame", "y_f32", "c_f32")}
+_CRC_POLY, _CRC_ONE = 0xEDB88320, 0x80000000
+
+
+def _crc_mulmod(a, b):
+    """a(x) * b(x) modulo the CRC-32 polynomial, in the CRC's reflected bit order (bit 31 is x^0)"""
+    p = 0
+    while a:
+        if a & _CRC_ONE:
+            p ^= b
+        a = (a << 1) & 0xffffffff
+        b = (b >> 1) ^ (_CRC_POLY if b & 1 else 0)
+    return p
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(A + B) from crc_a = zlib.crc32(A), crc_b = zlib.crc32(B) and len_b = len(B) (zlib's crc32_combine, which
+    the standard library does not expose): crc_a * x^(8 len_b) + crc_b modulo the CRC polynomial.  Pure Python."""
+    if len_b < 0:
+        raise ValueError("len_b must not be negative")
+    power, square, n = _CRC_ONE, _CRC_ONE >> 8, int(len_b)           # x^0; x^8, squared once per bit of len_b
+    while n:
+        if n & 1:
+            power = _crc_mulmod(square, power)
+        square = _crc_mulmod(square, square)
+        n >>= 1
+    return _crc_mulmod(power, crc_a & 0xffffffff) ^ (crc_b & 0xffffffff)
+
+
+def picture_hashes(frames_rec, pic_height, pic_width, level):
+    """CRC-32 of reconstructed (padded, float) pictures, taken on the device in ONE ops.crc32 call for all of them.
+    -> per frame {"y", "cb", "cr": of the cropped, rounded planes as frames_to_u8 writes them (ops.planes_to_u8), "frame":
+    of the three in file order (crc32_combine), the CRC-32 of the frame's bytes in the .yuv}; level "f32" adds "y_f32" and
+    "c_f32", of the padded float32 luma and chroma tensors as stored, the stricter check."""
+    from pMCTF.hip import ops
+    if level not in HASH_LEVELS:
+        raise ValueError(f"level is one of {HASH_LEVELS} (got {level!r})")
+    hc, wc = pic_height // 2, pic_width // 2
+    per_frame = len(HASH_KEYS[level]) - 1
+    tensors = []
+    for rec_y, rec_c, _ in frames_rec:
+        y, c = rec_y.contiguous(), rec_c.contiguous()
+        c8 = ops.planes_to_u8(c, hc, wc)
+        tensors += [ops.planes_to_u8(y, pic_height, pic_width), c8[0], c8[1]]
+        if level == "f32":
+            tensors += [y, c]
+    crcs = ops.crc32(tensors)
+    out = []
+    for i in range(len(frames_rec)):
+        v = crcs[i * per_frame:(i + 1) * per_frame]
+        rec = {"y": v[0], "cb": v[1], "cr": v[2],
+               "frame": crc32_combine(crc32_combine(v[0], v[1], hc * wc), v[2], hc * wc)}
+        if level == "f32":
+            rec.update(y_f32=v[3], c_f32=v[4])
+        out.append(rec)
+    return out
+
+
+def _check_hash_records(path, level, frames, frame_num=None):
+    if level not in HASH_LEVELS:
+        raise ValueError(f"{path}: level {level!r}, this decoder knows {HASH_LEVELS}")
+    if not isinstance(frames, list) or (frame_num is not None and len(frames) != frame_num):
+        got = len(frames) if isinstance(frames, list) else None
+        raise ValueError(f"{path}: {got!r} frame records, the sequence has {frame_num}")
+    for i, rec in enumerate(frames):
+        if not isinstance(rec, dict) or set(rec) != set(HASH_KEYS[level]):
+            raise ValueError(f"{path}: frame {i}: a record of level {level!r} holds exactly {HASH_KEYS[level]}")
+        for k, v in rec.items():
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 0xffffffff:
+                raise ValueError(f"{path}: frame {i}: {k} is not a 32-bit value ({v!r})")
+
+
+def write_picture_hashes(bin_folder, level, frames):
+    """bin_folder/picture_hashes.json: format version, level and one picture_hashes record per frame in display order"""
+    import json
+    path = os.path.join(bin_folder, PICTURE_HASHES)
+    _check_hash_records(path, level, frames)
+    record = {"format_version": PICTURE_HASH_FORMAT_VERSION, "level": level,
+              "frames": [{k: int(rec[k]) for k in HASH_KEYS[level]} for rec in frames]}
+    with open(path, "w") as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return path
+
+
+def read_picture_hashes(bin_folder, frame_num):
+    """-> {"format_version", "level", "frames"}; ValueError naming the path for a missing or malformed file, another
+    version, an unknown level or a frame list that does not have frame_num well-formed records"""
+    import json
+    path = os.path.join(bin_folder, PICTURE_HASHES)
+    try:
+        with open(path) as f:
+            record = json.load(f)
+    except FileNotFoundError:
+        raise ValueError(f"{path}: missing (the sequence was coded without picture_hash)") from None
+    except json.JSONDecodeError as e:
+        raise ValueError(f"{path}: not a picture hash file ({e})") from None
+    if not isinstance(record, dict) or record.get("format_version") != PICTURE_HASH_FORMAT_VERSION:
+        got = record.get("format_version") if isinstance(record, dict) else None
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {PICTURE_HASH_FORMAT_VERSION}")
+    if set(record) != {"format_version", "level", "frames"}:
+        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version, level and frames")
+    _check_hash_records(path, record["level"], record["frames"], frame_num)
+    return record
+
+
+class PictureHashMismatch(ValueError):
+    """a decoded picture is not the one the encoder reconstructed; .mismatch: {"gop", "folder", "frame", "plane",
+    "decoded", "recorded"}"""
+
+    def __init__(self, mismatch):
+        self.mismatch = dict(mismatch)
+        super().__init__(describe_hash_mismatch(mismatch))
+
+
+def describe_hash_mismatch(m):
+    where = f"{m['folder']}: " if m.get("folder") else ""
+    return (f"{where}frame {m['frame']}, plane {m['plane']}: decoded picture hashes to {m['decoded']:#010x}, the encoder "
+            f"recorded {m['recorded']:#010x}")
+
+
+def compare_hash_records(decoded, recorded, first_frame=0, **where):
+    """mismatches between two lists of picture_hashes records, on the keys of the recorded ones, frame by frame in key
+    order -> [{**where, "frame", "plane", "decoded", "recorded"}]"""
+    out = []
+    for i, (got, want) in enumerate(zip(decoded, recorded)):
+        out += [dict(where, frame=first_frame + i, plane=k, decoded=got[k], recorded=want[k])
+                for k in HASH_KEYS["f32"] if k in want and got[k] != want[k]]
+    return out
+
+
+def check_yuv_hashes(bin_folder, yuv_path):
+    """A decoded planar 4:2:0 file against bin_folder's picture_hashes.json at the u8 level, on the host with zlib alone
+    -> (frames checked, mismatches as compare_hash_records lists them).  ValueError for a file of the wrong length."""
+    import zlib
+    header = read_sequence_header(bin_folder)
+    recorded = read_picture_hashes(bin_folder, header["frame_num"])["frames"]
+    h, w = header["height"], header["width"]
+    ny, nc = h * w, (h // 2) * (w // 2)
+    if os.path.getsize(yuv_path) != header["frame_num"] * (ny + 2 * nc):
+        raise ValueError(f"{yuv_path}: {os.path.getsize(yuv_path)} bytes, {header['frame_num']} pictures of {w}x{h} have "
+                         f"{header['frame_num'] * (ny + 2 * nc)}")
+    decoded = []
+    with open(yuv_path, "rb") as f:
+        for _ in recorded:
+            data = f.read(ny + 2 * nc)
+            decoded.append({"y": zlib.crc32(data[:ny]), "cb": zlib.crc32(data[ny:ny + nc]), "cr": zlib.crc32(data[ny + nc:]),
+                            "frame": zlib.crc32(data)})
+    u8 = [{k: rec[k] for k in HASH_KEYS["u8"]} for rec in recorded]
+    return len(decoded), compare_hash_records(decoded, u8, folder=yuv_path)
+
+
 def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
     """Decode a folder written by encode_sequence(keep_gops=True) into a planar 8-bit 4:2:0 file (the layout YUVReader
     reads), GOP by GOP.  The codec holds the weights the sequence was coded with; its number of motion stages, arithmetic
     profile and ATen thread setting must equal the header's (ValueError otherwise).  device: checked against the
     codec's, if given.  png_out: a folder that receives every decoded picture as {index}.png (frames_to_rgb8, write_pngs);
     yuv_out may then be None (PNGs only).
-    Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP}."""
+    A folder that holds picture hashes (encode_sequence(picture_hash=...)) is checked against them:
+    decode_sequence_checked with verify="auto", which also has the other modes.  Its parameters stay these five.
+    Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP, "verified": pictures checked,
+    "hash_mismatches": []}."""
+    return decode_sequence_checked(codec, bin_folder, yuv_out, device, png_out, verify="auto")
+
+
+def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto"):
+    """decode_sequence with the choice of what to do with the folder's picture_hashes.json.  verify="auto" (what
+    decode_sequence does): check every decoded picture against it when it is there, nothing otherwise; True: the same,
+    and a ValueError when it is missing; False: never look at it; "report": check, write every picture all the same and
+    return the mismatches.  The hashes are taken on the device (picture_hashes, at the file's level) before anything of a
+    GOP is written; under "auto" and True the first mismatch raises PictureHashMismatch (a ValueError naming the GOP's
+    folder, the frame, the plane and both values) with none of that GOP's pictures written.
+    Returns decode_sequence's dict: "verified" counts the pictures checked, "hash_mismatches" lists {"gop", "folder",
+    "frame", "plane", "decoded", "recorded"}."""
     import contextlib
     import time
+    if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
+        raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
     if yuv_out is None and png_out is None:
         raise ValueError("nothing to write: give yuv_out, png_out or both")
     header = read_sequence_header(bin_folder)
@@ -734,14 +925,26 @@ def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
     dev = codec.engine().dev
     if device is not None and torch.device(device).type != dev.type:
         raise ValueError(f"the codec lives on {dev}, not on {device}")
+    recorded = None
+    if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
+        recorded = read_picture_hashes(bin_folder, header["frame_num"])
     h, w = header["height"], header["width"]
-    shapes, seconds = [], []
+    shapes, seconds, mismatches, verified = [], [], [], 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
         for k in range(header["frame_num"] // header["gop"]):
             t0 = time.time()
-            out = decode_gop_files(codec, os.path.join(bin_folder, gop_folder(k)), header["gop"], h, w, header["q_index"],
+            folder = os.path.join(bin_folder, gop_folder(k))
+            out = decode_gop_files(codec, folder, header["gop"], h, w, header["q_index"],
                                    psize=header["psize"], me_downsample=header["me_downsample"],
                                    ll_order=header["ll_order"])
+            if recorded is not None:
+                first = k * header["gop"]
+                bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"]),
+                                           recorded["frames"][first:first + header["gop"]], first, gop=k, folder=folder)
+                if bad and verify != "report":
+                    raise PictureHashMismatch(bad[0])
+                mismatches += bad
+                verified += header["gop"]
             if f is not None:
                 for planes in frames_to_u8(out["frames"], h, w):
                     for p in planes:
@@ -750,4 +953,4 @@ def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
                 write_pngs(png_out, k * header["gop"], frames_to_rgb8(out["frames"], h, w))
             shapes += [(h, w)] * header["gop"]
             seconds.append(time.time() - t0)
-    return {"header": header, "frames": shapes, "seconds": seconds}
+    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches}

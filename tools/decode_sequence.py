@@ -7,7 +7,9 @@
 
 The number of motion stages comes from the folder's sequence.json; the weights must be the ones the sequence was coded
 with.  The decoder refuses a header whose arithmetic profile (PMCTF_PRECISION) or ATen thread setting
-(PMCTF_ATEN_THREADS) differs from this process's."""
+(PMCTF_ATEN_THREADS) differs from this process's.  A folder coded with --picture-hash holds the encoder's picture hashes:
+every decoded picture is checked against them (a mismatch stops the decoder before that GOP is written) unless --no-verify
+is given; --verify insists on the hashes being there, --verify-report writes everything and lists the mismatches."""
 import argparse
 import json
 import os
@@ -24,6 +26,12 @@ def main():
     w.add_argument("--synth-seed", type=int, help="deterministic synthetic weights (pmctf_synth) with this seed")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--png", metavar="DIR", help="also write every decoded picture there as {index}.png (RGB)")
+    v = ap.add_mutually_exclusive_group()
+    v.add_argument("--verify", dest="verify", action="store_const", const=True, default="auto",
+                   help="check the picture hashes and fail when the folder has none (default: check them when it has)")
+    v.add_argument("--no-verify", dest="verify", action="store_const", const=False, help="do not check picture hashes")
+    v.add_argument("--verify-report", dest="verify", action="store_const", const="report",
+                   help="check, write every picture all the same, list the mismatches and exit with status 1 if there are any")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args()
@@ -43,10 +51,18 @@ def main():
     net = net.to(a.device)
     net.update(force=True)
     with torch.no_grad():
-        out = pmctf_gop.decode_sequence(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png)
+        try:
+            out = pmctf_gop.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png, verify=a.verify)
+        except pmctf_gop.PictureHashMismatch as e:
+            sys.exit(f"picture hash mismatch: {e}")
     n = len(out["frames"])
     print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out, "png": a.png,
-                      "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9)}))
+                      "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
+                      "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"])}))
+    for m in out["hash_mismatches"]:
+        print(pmctf_gop.describe_hash_mismatch(m), file=sys.stderr)
+    if out["hash_mismatches"]:
+        sys.exit(1)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,9 @@ JSON record.
 
 SOURCE is a planar 8-bit 4:2:0 file (--width and --height required) or a folder of PNG pictures, taken in natural numeric
 order and converted to 4:2:0 on the GPU (their size is read from the files).  tools/decode_sequence.py reads BIN_FOLDER
-back with the same weights."""
+back with the same weights.  --picture-hash u8|f32 also records the CRC-32 of every reconstructed picture
+(BIN_FOLDER/picture_hashes.json), which the decoder then checks; tools/check_picture_hashes.py checks a decoded .yuv against
+it without a GPU."""
 import argparse
 import os
 import sys
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--height", type=int, help="picture height (.yuv sources)")
     ap.add_argument("--decoded-frames", metavar="DIR", help="save every reconstructed frame there as {index}.png")
     ap.add_argument("--msssim", action="store_true", help="fill the MS-SSIM fields of the record (GPU quality kernels)")
+    ap.add_argument("--picture-hash", choices=("u8", "f32"),
+                    help="record picture hashes: of the written 8-bit planes (u8), and of the padded float32 reconstructions (f32)")
     ap.add_argument("source", help=".yuv file or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args()
@@ -66,7 +70,7 @@ def main():
     with torch.no_grad():
         out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
                                         src_format=src_format, decoded_frame_path=a.decoded_frames, keep_gops=True,
-                                        msssim=a.msssim)
+                                        msssim=a.msssim, picture_hash=a.picture_hash)
     print(out["json"])
 
 
