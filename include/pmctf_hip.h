@@ -449,6 +449,32 @@ int pmctf_yuv420_u8_to_planes_f32(const uint8_t *src, float *y_pad, float *c_pad
 int pmctf_rgb8_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int h, int w, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * High-bit-depth pictures in and out (csrc/picture_hbd.hip): planar 4:2:0 sources of bitdepth b = 9..16, every sample a
+ * little-endian 16-bit word (yuv420p10le / p12le / p16le).  The codec's float planes keep their 0..255 range: with
+ * s = b - 8 and max = 2^b - 1 a sample v enters as v * 2^-s (exact for every 16-bit v) and a reconstruction x leaves as
+ * rint(clamp(x * 2^s, 0, max)), ties to even, NaN -> 0; out(in(v)) == v for every v <= max.  No synchronisation.
+ * PMCTF_EINVAL, before anything is launched, for a null pointer (the two originals of the first may be null), a
+ * bitdepth outside 9..16, a pointer less aligned than its element type, Hp < h or Wp < w, and sizes that are not
+ * positive or above 16384; the first and the third take whole pictures and want h, w, Hp, Wp even as well.
+ *
+ * pmctf_yuv420_u16_to_planes_f32: the 16-bit pmctf_yuv420_u8_to_planes_f32.  src: h*w luma samples, then two planes of
+ *   (h/2)*(w/2), 2-byte aligned (samples above max are converted as they are) -> y_pad (1,1,Hp,Wp), c_pad
+ *   (2,1,Hp/2,Wp/2), zero outside the picture (16-byte aligned) and, unless null, y_org (1,1,h,w), c_org (2,1,h/2,w/2).
+ *   One launch.
+ * pmctf_planes_to_u16: the 16-bit pmctf_planes_to_u8.  x (N,1,Hp,Wp) -> out (N,h,w) samples, 2-byte aligned; any
+ *   positive h <= Hp, w <= Wp (the chroma planes of a 6x10 picture are 3x5); N*Hp*Wp < 2^31.  One launch.
+ * pmctf_frame_sse_u16_f32: rec_y (1,1,Hp,Wp), rec_c (2,1,Hp/2,Wp/2) padded, neither clamped nor rounded; org_y (1,1,h,w),
+ *   org_c (2,1,h/2,w/2) the originals as the first function returns them -> sse3[0..2] = sum of (v_hat - v)^2 over Y, Cb,
+ *   Cr with v_hat = rint(clamp(rec * 2^s, 0, max)) and v = org * 2^s: integers, accumulated in 64 bits (one term can be
+ *   65535^2), exact and the same on every run (integer atomic adds, one per workgroup and plane).  sse3: three values on
+ *   the device, 8-byte aligned.  One clear of sse3 and one launch. */
+int pmctf_yuv420_u16_to_planes_f32(const uint16_t *src, float *y_pad, float *c_pad, float *y_org, float *c_org, int Hp,
+                                   int Wp, int h, int w, int bitdepth, void *stream);
+int pmctf_planes_to_u16(const float *x, uint16_t *out, int N, int Hp, int Wp, int h, int w, int bitdepth, void *stream);
+int pmctf_frame_sse_u16_f32(const float *rec_y, const float *rec_c, const float *org_y, const float *org_c, int Hp, int Wp,
+                            int h, int w, int bitdepth, uint64_t *sse3, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Picture hashes (csrc/picture_hash.hip): crc_out[s] = CRC-32 of the bytes [data, data + bytes) of segs[s], s < n_segs, as
  * zlib.crc32 computes it (reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF).  The encoder records
  * the hashes of its reconstructed pictures, the decoder recomputes and compares them (pmctf_gop.picture_hashes).

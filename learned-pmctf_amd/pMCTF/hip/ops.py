@@ -667,7 +667,110 @@ def rgb8_to_yuv420(rgb_u8):
     return out
 
 
-CRC32_TILE_BYTES = 4096                    # PMCTF_CRC32_TILE_BYTES of include/pmctf_hip.h
+# ------------------------------------------------------------------------------------------------
+# high-bit-depth pictures in and out (csrc/picture_hbd.hip): 16-bit samples travel as torch.uint16
+HBD_MIN, HBD_MAX = 9, 16
+
+
+def _pu16(t):
+    assert t.is_cuda and t.dtype == torch.uint16 and t.is_contiguous(), "expect dense uint16 device tensor"
+    return C.c_void_p(t.data_ptr())
+
+
+def _bitdepth(bitdepth):
+    b = int(bitdepth)
+    if not HBD_MIN <= b <= HBD_MAX:
+        raise ValueError(f"a 16-bit sample holds a bitdepth of {HBD_MIN}..{HBD_MAX} (got {bitdepth})")
+    return b
+
+
+def planes_from_u16(frame_u16, h, w, bitdepth, psize=128, originals=True):
+    """planes_from_u8 for one picture of a planar 4:2:0 file of `bitdepth` 9..16 (uint16 device tensor of h*w*3/2 samples,
+    as little-endian words lie in the file): every sample v becomes v * 2^-(bitdepth - 8), exactly, so the planes keep the
+    codec's 0..255 range.  -> (y_pad, c_pad, y_org, c_org) float32 as planes_from_u8.  One launch; the counterpart of
+    planes_to_u16."""
+    from ..utils.stream_helper import get_padding_size
+    h, w = _picture_size(h, w)
+    bitdepth = _bitdepth(bitdepth)
+    psize = int(psize)
+    if psize <= 0 or psize & 1:
+        raise ValueError(f"psize must be even and positive (got {psize})")
+    if not isinstance(frame_u16, torch.Tensor) or frame_u16.dtype != torch.uint16:
+        raise ValueError("expect a uint16 tensor")
+    if frame_u16.numel() != h * w * 3 // 2:
+        raise ValueError(f"a {h}x{w} 4:2:0 picture has {h * w * 3 // 2} samples, got {frame_u16.numel()}")
+    dev = _dev(frame_u16)
+    frame_u16 = frame_u16.contiguous()
+    _, right, _, bottom = get_padding_size(h, w, p=psize)
+    Hp, Wp = h + bottom, w + right
+    if max(Hp, Wp) > PICTURE_MAX_SIDE:
+        raise ValueError(f"padded size {Hp}x{Wp} exceeds {PICTURE_MAX_SIDE}")
+    y_pad = torch.empty((1, 1, Hp, Wp), dtype=torch.float32, device=dev)
+    c_pad = torch.empty((2, 1, Hp // 2, Wp // 2), dtype=torch.float32, device=dev)
+    y_org = torch.empty((1, 1, h, w), dtype=torch.float32, device=dev) if originals else None
+    c_org = torch.empty((2, 1, h // 2, w // 2), dtype=torch.float32, device=dev) if originals else None
+    _lib.check(_lib.hip().pmctf_yuv420_u16_to_planes_f32(_pu16(frame_u16), _p(y_pad), _p(c_pad), _p(y_org), _p(c_org), Hp,
+                                                         Wp, h, w, bitdepth, _stream()), "planes_from_u16")
+    return y_pad, c_pad, y_org, c_org
+
+
+def planes_to_u16(x, h, w, bitdepth):
+    """planes_to_u8 for a `bitdepth` of 9..16: padded planes (N,1,Hp,Wp) float32 -> cropped (N,h,w) uint16,
+    rint(clamp(x * 2^(bitdepth - 8), 0, 2^bitdepth - 1)), ties to even, NaN -> 0.  One launch."""
+    bitdepth = _bitdepth(bitdepth)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError("expect a float32 tensor of planes (N,1,Hp,Wp)")
+    N, _, Hp, Wp = x.shape
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or h > Hp or w > Wp or max(Hp, Wp) > PICTURE_MAX_SIDE:
+        raise ValueError(f"plane size {h}x{w} must be positive and inside the padded {Hp}x{Wp} (at most {PICTURE_MAX_SIDE})")
+    dev = _dev(x)
+    out = torch.empty((N, h, w), dtype=torch.uint16, device=dev)
+    _lib.check(_lib.hip().pmctf_planes_to_u16(_p(x.contiguous()), _pu16(out), N, Hp, Wp, h, w, bitdepth, _stream()),
+               "planes_to_u16")
+    return out
+
+
+def psnr_from_sse_hbd(sse, n, bitdepth):
+    """10 log10(max^2 n / sse) with max = 2^bitdepth - 1, float64 on the host; inf for sse == 0"""
+    import math
+    return math.inf if sse == 0 else 10.0 * math.log10(float((1 << bitdepth) - 1) ** 2 * n / sse)
+
+
+def frame_sse_hbd(rec_y, rec_c, org_y, org_c, h, w, bitdepth):
+    """Quality of one reconstructed frame at `bitdepth` 9..16 bits: rec_y (1,1,Hp,Wp) / rec_c (2,1,Hp/2,Wp/2) padded, neither
+    clamped nor rounded; org_y (1,1,h,w) / org_c (2,1,h/2,w/2) the originals as planes_from_u16 / read_gop return them.
+    Both are taken back to `bitdepth`-bit integers (planes_to_u16's rounding for the reconstruction) and the squared
+    differences are summed in 64-bit integers on the device.
+    -> {"y","cb","cr","yuv": PSNR in dB against 2^bitdepth - 1 (inf for identical planes), "sse": (Y, Cb, Cr) ints}.
+    One launch and one device->host copy."""
+    h, w = int(h), int(w)
+    bitdepth = _bitdepth(bitdepth)
+    for t in (rec_y, rec_c, org_y, org_c):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("expect float32 tensors")
+    rec_y, rec_c, org_y, org_c = (t.contiguous() for t in (rec_y, rec_c, org_y, org_c))
+    Hp, Wp = rec_y.shape[-2:]
+    if h <= 0 or w <= 0 or (h | w) & 1 or h > Hp or w > Wp or (Hp | Wp) & 1 or max(Hp, Wp) > PICTURE_MAX_SIDE:
+        raise ValueError(f"picture size {h}x{w} must be even, positive and inside the even padded {Hp}x{Wp}")
+    if tuple(rec_c.shape) != (2, 1, Hp // 2, Wp // 2) or tuple(org_y.shape[-2:]) != (h, w) or \
+            tuple(org_c.shape) != (2, 1, h // 2, w // 2) or rec_y.numel() != Hp * Wp or org_y.numel() != h * w:
+        raise ValueError("expect luma (1,1,Hp,Wp) / chroma (2,1,Hp/2,Wp/2) reconstructions and un-padded originals")
+    dev = _dev(rec_y)
+    for t in (rec_c, org_y, org_c):
+        _dev(t)
+    out = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.check(_lib.hip().pmctf_frame_sse_u16_f32(_p(rec_y), _p(rec_c), _p(org_y), _p(org_c), Hp, Wp, h, w, bitdepth,
+                                                  C.c_void_p(out.data_ptr()), _stream()), "frame_sse_hbd")
+    sse = tuple(v & 0xffffffffffffffff for v in out.cpu().tolist())          # the frame's one copy to the host
+    n = h * w
+    res = {"y": psnr_from_sse_hbd(sse[0], n, bitdepth), "cb": psnr_from_sse_hbd(sse[1], n // 4, bitdepth),
+           "cr": psnr_from_sse_hbd(sse[2], n // 4, bitdepth), "sse": sse}
+    res["yuv"] = (6.0 * res["y"] + res["cb"] + res["cr"]) / 8.0
+    return res
+
+
+CRC32_TILE_BYTES = 4096                   # PMCTF_CRC32_TILE_BYTES of include/pmctf_hip.h
 CRC32_MAX_SEGMENTS = 65535
 
 

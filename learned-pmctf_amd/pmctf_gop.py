@@ -233,8 +233,36 @@ def gop_quality(frames_rec, frames_orig, pic_height, pic_width, msssim=True):
     return out
 
 
+def gop_quality_hbd(frames_rec, frames_orig, pic_height, pic_width, bitdepth):
+    """gop_quality for a source of `bitdepth` 9..16 bits: reconstruction and originals are taken back to integers of that
+    depth (pMCTF.hip.ops.frame_sse_hbd: planes_to_u16's rounding, 64-bit integer error sums on the device) and the PSNR is
+    against 2^bitdepth - 1.  -> [{"y","cb","cr","yuv","rgb","msssim","sse": (Y, Cb, Cr)}] with "rgb" and "msssim" 0.0: the
+    harness defines RGB-PSNR and MS-SSIM on 8-bit RGB pictures.  gop_quality keeps its five parameters; this is its
+    high-bit-depth form.  No CPU fallback."""
+    from pMCTF.hip import ops
+    bitdepth = check_bitdepth(bitdepth, above8=True)
+    out = []
+    for rec, (y, c) in zip(frames_rec, frames_orig):
+        tensors = (rec[0], rec[1], y, c)
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+            raise RuntimeError("gop_quality_hbd runs on the GPU (no CPU fallback): pass device tensors")
+        rec_y, rec_c, y, c = (t.float().contiguous() for t in tensors)
+        q = ops.frame_sse_hbd(rec_y, rec_c, y, c, pic_height, pic_width, bitdepth)
+        q.update(rgb=0.0, msssim=0.0)
+        out.append(q)
+    return out
+
+
+def check_bitdepth(bitdepth, above8=False):
+    """the source bit depth as an int: 8, or 9..16 (16-bit samples); ValueError otherwise, and for 8 with above8"""
+    if isinstance(bitdepth, bool) or not isinstance(bitdepth, int) or not (8, 9)[above8] <= bitdepth <= 16:
+        raise ValueError(f"bitdepth is {'' if above8 else '8 or '}9..16 (got {bitdepth!r})")
+    return bitdepth
+
+
 def write_yuv(path, frames_u8):
-    """[(Y, Cb, Cr) uint8 arrays] -> planar 8-bit 4:2:0 file, the layout YUVReader / image_import read"""
+    """[(Y, Cb, Cr) uint8 arrays] -> planar 8-bit 4:2:0 file, the layout YUVReader / image_import read; uint16 arrays
+    give the 16-bit layout of YUVReader(bitdepth=9..16) (the samples are written in the host's byte order: little-endian)"""
     with open(path, "wb") as f:
         for planes in frames_u8:
             for p in planes:
@@ -244,12 +272,18 @@ def write_yuv(path, frames_u8):
 def read_gop(reader, gop, device, psize=128):
     """GOP pictures from a YUVReader as the model's inputs: ([Y (1,1,Hp,Wp), UV (2,1,Hp/2,Wp/2)] zero padded right/bottom
     to multiples of psize (chroma psize/2), the un-padded originals, (height, width)).  What the harness does per pair
-    at stage 0 (test_pMCTF_flex.py:151-192), done here per GOP."""
+    at stage 0 (test_pMCTF_flex.py:151-192), done here per GOP.  A reader of 16-bit samples (YUVReader(bitdepth=b)) has them
+    scaled by 2^-(b - 8)."""
     import torch.nn.functional as F
     from pMCTF.utils.stream_helper import get_padding_size
     padded, orig, size = [], [], None
+    shift = getattr(reader, "bitdepth", 8) - 8
     for _ in range(gop):
-        y, cb, cr = (torch.from_numpy(p).float() for p in reader.read_one_frame())
+        if shift:                                   # b-bit samples enter as v * 2^-(b - 8): exact, the range stays 0..255
+            import numpy as np
+            y, cb, cr = (torch.from_numpy(p.astype(np.float32)) * 2.0 ** -shift for p in reader.read_one_frame())
+        else:
+            y, cb, cr = (torch.from_numpy(p).float() for p in reader.read_one_frame())
         assert size in (None, tuple(y.shape)), "picture size changes inside the sequence"
         size = tuple(y.shape)
         luma = y[None, None].to(device)
@@ -326,11 +360,12 @@ def read_gop_device(reader, gop, device, psize=128):
     """read_gop with the arithmetic on the device: the same triple, tensor for tensor and bit for bit.  From a YUVReader a
     picture costs one copy of its bytes to the device and one launch (pmctf_yuv420_u8_to_planes_f32: conversion, padding
     and the un-padded originals); from a PNGReader the RGB bytes are copied and converted to 4:2:0 first
-    (pmctf_rgb8_to_yuv420_u8)."""
+    (pmctf_rgb8_to_yuv420_u8).  A YUVReader of 16-bit samples goes through pmctf_yuv420_u16_to_planes_f32 the same way."""
     import numpy as np
     from pMCTF.hip import ops
     _need_gpu(device, "read_gop_device")
     padded, orig, size = [], [], None
+    bitdepth = getattr(reader, "bitdepth", 8)
     for _ in range(gop):
         pic = reader.read_one_frame()
         assert pic is not None, "sequence ends inside a GOP"
@@ -342,7 +377,10 @@ def read_gop_device(reader, gop, device, psize=128):
             frame = torch.from_numpy(np.concatenate([p.reshape(-1) for p in pic])).to(device)
         assert size in (None, shape), "picture size changes inside the sequence"
         size = shape
-        y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, size[0], size[1], psize=psize)
+        if bitdepth > 8:
+            y_pad, c_pad, y_org, c_org = ops.planes_from_u16(frame, size[0], size[1], bitdepth, psize=psize)
+        else:
+            y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, size[0], size[1], psize=psize)
         orig.append([y_org, c_org])
         padded.append([y_pad, c_pad])
     return padded, orig, size
@@ -371,7 +409,7 @@ def rgb_psnr(rec_y, rec_c, y, c):
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
                     skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
-                    picture_hash=None, keep_gops=False, msssim=False):
+                    picture_hash=None, bitdepth=8, keep_gops=False, msssim=False):
     """What the evaluation harness produces for one sequence (test_pMCTF_flex.py:run_test, 86-346) built from this
     module's own pieces: pictures come from a planar .yuv through YUVReader and get_padding_size, every closed GOP goes
     through encode_gop (one encode_one_stage call per pair, both per-pair report lines), decode_gop and gop_psnr, and
@@ -391,6 +429,12 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     picture_hash="u8" or "f32" (needs keep_gops=True; default None: off, no file): the CRC-32 of every reconstructed picture,
     taken on the device (picture_hashes), goes to bin_folder/picture_hashes.json, where decode_sequence finds and checks
     it; the result gains "picture_hashes".  sequence.json is the same either way.
+    bitdepth=9..16 (keyword; default 8: everything above): yuv_path holds little-endian 16-bit samples of that depth
+    (yuv420p10le and its like; src_format "yuv" only, either ingest).  A sample v enters the codec as v * 2^-(bitdepth - 8),
+    so a source whose samples are all multiples of 2^(bitdepth - 8) codes to the very files of its 8-bit form.  The quality
+    tables come from gop_quality_hbd: "psnr" is the YUV-PSNR at that depth, "psnr_rgb" 0.0 per frame; msssim=True and
+    decoded_frame_path are refused (ValueError), picture_hash is "u16" or "f32".  With keep_gops=True bin_folder also gets
+    picture_format.json (write_picture_format), which tells decode_sequence the depth.
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
     import io
     import time
@@ -398,6 +442,16 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
         raise ValueError(f"picture_hash is None or one of {HASH_LEVELS} (got {picture_hash!r})")
     if picture_hash is not None and not keep_gops:
         raise ValueError("picture_hash needs keep_gops=True: the hashes belong to a folder decode_sequence can read")
+    bitdepth = check_bitdepth(bitdepth)
+    if picture_hash is not None:
+        check_hash_level(picture_hash, bitdepth)
+    if bitdepth > 8:
+        if src_format == "png":
+            raise ValueError(f"bitdepth {bitdepth}: a source above 8 bits is a .yuv file (src_format='yuv'), PNG input is 8-bit")
+        if msssim:
+            raise ValueError(f"bitdepth {bitdepth}: MS-SSIM and RGB-PSNR are defined on 8-bit RGB pictures (msssim=False)")
+        if decoded_frame_path is not None:
+            raise ValueError(f"bitdepth {bitdepth}: decoded_frame_path writes 8-bit PNGs; decode the folder to a .yuv instead")
     from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
     from pMCTF.utils.yuv_reader import YUVReader
     assert frame_num % gop == 0
@@ -413,7 +467,7 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
         if len(reader) < frame_num:
             raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
     else:
-        reader = YUVReader(yuv_path, width, height, start_index=0)
+        reader = YUVReader(yuv_path, width, height, start_index=0, bitdepth=bitdepth)
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines = []
     ssims = []
@@ -437,15 +491,18 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
             lines += enc["log"]
             rec = decode_gop(codec, enc["frames_coded"])
             if picture_hash is not None:
-                hashes += picture_hashes(rec, h, w, picture_hash)
+                hashes += picture_hashes(rec, h, w, picture_hash, bitdepth)
             if decoded_frame_path is not None:
                 write_pngs(decoded_frame_path, first_frame, frames_to_rgb8(rec, h, w))
-            quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
+            if bitdepth > 8:
+                quality = gop_quality_hbd(rec, orig, h, w, bitdepth)
+            else:
+                quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
             tables["bits"] += enc["bits"]
             tables["bpp_mv"] += [b / (h * w) for b in enc["bits_mv"]]
             tables["psnr"] += [p["yuv"] for p in quality]
             tables["frame_types"] += [0] + [1] * (gop - 1)          # the one coded L picture of a GOP, then its H pictures
-            if msssim:
+            if msssim or bitdepth > 8:
                 tables["psnr_rgb"] += [p["rgb"] for p in quality]
                 ssims += [p["msssim"] for p in quality]
                 continue
@@ -460,6 +517,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                               **codec_header_fields(codec))
         if picture_hash is not None:
             write_picture_hashes(bin_folder, picture_hash, hashes)
+        if bitdepth > 8:
+            write_picture_format(bin_folder, bitdepth)
     for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
         lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
     record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
@@ -483,9 +542,11 @@ def quality_line(idx, q, bpp=None, seconds=None):
             f"Y-PSNR: {q['y']:.4f},  Cb-PSNR: {q['cb']:.4f}, Cr-PSNR: {q['cr']:.4f}  ")
 
 
-def sequence_quality(src_yuv, rec_yuv, width, height, frame_num, device, gop=None, msssim=True):
+def sequence_quality(src_yuv, rec_yuv, width, height, frame_num, device, gop=None, msssim=True, bitdepth=8):
     """Quality of a decoded planar 8-bit 4:2:0 file against its source, frame by frame, through YUVReader and gop_quality
-    (the files -> .yuv -> quality end of the loop decode_sequence opens).
+    (the files -> .yuv -> quality end of the loop decode_sequence opens).  bitdepth=9..16: both files hold 16-bit samples
+    of that depth and the numbers come from gop_quality_hbd (PSNR against 2^bitdepth - 1, "sse" (Y, Cb, Cr); "psnr_rgb" and
+    "msssim" are 0.0 whatever msssim says: they are defined on 8-bit RGB).
     -> {"psnr" (YUV), "psnr_rgb", "msssim", "psnr_y", "psnr_cb", "psnr_cr": per-frame lists, "sse": [(Y, Cb, Cr, RGB)],
         "mean": {table: mean}, "frame_types": [0] + [1] * (gop - 1) per GOP when gop is given (as encode_sequence), else
         None, "lines": one report line per frame}."""
@@ -496,11 +557,12 @@ def sequence_quality(src_yuv, rec_yuv, width, height, frame_num, device, gop=Non
         raise ValueError(f"4:2:0 pictures have even, positive sizes (got {width}x{height}, {frame_num} frames)")
     if gop is not None and (gop < 1 or frame_num % gop):
         raise ValueError(f"frame_num {frame_num} is not a multiple of gop {gop}")
-    frame_bytes = width * height + 2 * (width // 2) * (height // 2)
+    bitdepth = check_bitdepth(bitdepth)
+    frame_bytes = (width * height + 2 * (width // 2) * (height // 2)) * (2 if bitdepth > 8 else 1)
     for path in (src_yuv, rec_yuv):
         if os.path.getsize(path) < frame_num * frame_bytes:
             raise ValueError(f"{path}: shorter than {frame_num} pictures of {width}x{height}")
-    ro, rd = YUVReader(src_yuv, width, height, start_index=0), YUVReader(rec_yuv, width, height, start_index=0)
+    ro, rd = (YUVReader(p, width, height, start_index=0, bitdepth=bitdepth) for p in (src_yuv, rec_yuv))
     names = {"yuv": "psnr", "rgb": "psnr_rgb", "msssim": "msssim", "y": "psnr_y", "cb": "psnr_cb", "cr": "psnr_cr"}
     out = {v: [] for v in names.values()}
     out.update(sse=[], lines=[])
@@ -509,7 +571,10 @@ def sequence_quality(src_yuv, rec_yuv, width, height, frame_num, device, gop=Non
             # psize=2: nothing to pad (the sizes are even), the pictures go to the kernels as they are in the files
             _, orig, (h, w) = read_gop(ro, 1, device, psize=2)
             _, dec, _ = read_gop(rd, 1, device, psize=2)
-            q = gop_quality([(dec[0][0], dec[0][1], None)], orig, h, w, msssim=msssim)[0]
+            if bitdepth > 8:
+                q = gop_quality_hbd([(dec[0][0], dec[0][1], None)], orig, h, w, bitdepth)[0]
+            else:
+                q = gop_quality([(dec[0][0], dec[0][1], None)], orig, h, w, msssim=msssim)[0]
             for k, v in names.items():
                 out[v].append(q[k])
             out["sse"].append(q["sse"])
@@ -608,6 +673,48 @@ def check_sequence_header(header, codec_fields):
     if diff:
         raise ValueError("the sequence was coded with a different codec configuration: " +
                          ", ".join(f"{k} {a!r} in the header, {b!r} here" for k, (a, b) in sorted(diff.items())))
+
+
+PICTURE_FORMAT = "picture_format.json"
+PICTURE_FORMAT_VERSION = 1
+
+
+def write_picture_format(bin_folder, bitdepth):
+    """bin_folder/picture_format.json: {"format_version", "bitdepth"}, the depth 9..16 of the source's 16-bit samples.
+    Written beside sequence.json only for a source above 8 bits; the bitstream files and sequence.json do not know it."""
+    import json
+    path = os.path.join(bin_folder, PICTURE_FORMAT)
+    try:
+        bitdepth = check_bitdepth(bitdepth, above8=True)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    with open(path, "w") as f:
+        json.dump({"format_version": PICTURE_FORMAT_VERSION, "bitdepth": bitdepth}, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return path
+
+
+def read_picture_format(bin_folder):
+    """-> the bit depth of the folder's pictures: 8 when there is no picture_format.json, else the 9..16 it holds;
+    ValueError naming the path for a malformed file, another version, an unknown field or another depth"""
+    import json
+    path = os.path.join(bin_folder, PICTURE_FORMAT)
+    try:
+        with open(path) as f:
+            record = json.load(f)
+    except FileNotFoundError:
+        return 8
+    except (json.JSONDecodeError, UnicodeDecodeError) as e:
+        raise ValueError(f"{path}: not a picture format file ({e})") from None
+    if not isinstance(record, dict) or record.get("format_version") != PICTURE_FORMAT_VERSION:
+        got = record.get("format_version") if isinstance(record, dict) else None
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {PICTURE_FORMAT_VERSION}")
+    if set(record) != {"format_version", "bitdepth"}:
+        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version and bitdepth")
+    try:
+        return check_bitdepth(record["bitdepth"], above8=True)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
 
 
 def _read_framed(path, header_bytes):
@@ -709,6 +816,19 @@ def frames_to_u8(frames_rec, pic_height, pic_width):
     return [(y[0], c[0], c[1]) for y, c in host]
 
 
+def frames_to_u16(frames_rec, pic_height, pic_width, bitdepth):
+    """frames_to_u8 at a bitdepth of 9..16: -> [(Y, Cb, Cr)] uint16 arrays, rint(clamp(x * 2^(bitdepth - 8), 0, 2^bitdepth -
+    1)) of the un-padded size (pmctf_planes_to_u16); write_yuv writes them as the 16-bit file layout"""
+    from pMCTF.hip import ops
+    out = []
+    for rec_y, rec_c, _ in frames_rec:
+        y = ops.planes_to_u16(rec_y.contiguous(), pic_height, pic_width, bitdepth)
+        c = ops.planes_to_u16(rec_c.contiguous(), pic_height // 2, pic_width // 2, bitdepth)
+        out.append((y, c))
+    host = [(y.cpu().numpy(), c.cpu().numpy()) for y, c in out]
+    return [(y[0], c[0], c[1]) for y, c in host]
+
+
 def frames_to_rgb8(frames_rec, pic_height, pic_width):
     """reconstructed (padded, float) pictures -> [(h, w, 3) uint8 RGB arrays] of the un-padded size, the pictures the
     harness saves (test_pMCTF_flex.py:76-79,313-317): one launch (pmctf_yuv420_to_rgb8_f32) and one copy of bytes to the
@@ -739,8 +859,19 @@ def write_pngs(folder, first_index, pictures):
 # (check_yuv_hashes, tools/check_picture_hashes.py).
 PICTURE_HASHES = "picture_hashes.json"
 PICTURE_HASH_FORMAT_VERSION = 1
-HASH_LEVELS = ("u8", "f32")
-HASH_KEYS = {"u8": ("y", "cb", "cr", "frame"), "f32": ("y", "cb", "cr", "frame", "y_f32", "c_f32")}
+HASH_LEVELS = ("u8", "f32", "u16")
+HASH_KEYS = {"u8": ("y", "cb", "cr", "frame"), "f32": ("y", "cb", "cr", "frame", "y_f32", "c_f32"),
+             "u16": ("y", "cb", "cr", "frame")}
+
+
+def check_hash_level(level, bitdepth):
+    """the integer planes hashed are the ones written to the decoded file: bytes at 8 bits ("u8"), 16-bit samples above
+    ("u16"); "f32" adds the float tensors at either depth.  ValueError for a level that does not go with the depth."""
+    if level not in HASH_LEVELS:
+        raise ValueError(f"level is one of {HASH_LEVELS} (got {level!r})")
+    if level == ("u8" if bitdepth > 8 else "u16"):
+        raise ValueError(f"picture hash level {level!r} does not go with bitdepth {bitdepth}: "
+                         f"{'u16' if bitdepth > 8 else 'u8'} or f32")
 _CRC_POLY, _CRC_ONE = 0xEDB88320, 0x80000000
 
 
@@ -769,21 +900,28 @@ def crc32_combine(crc_a, crc_b, len_b):
     return _crc_mulmod(power, crc_a & 0xffffffff) ^ (crc_b & 0xffffffff)
 
 
-def picture_hashes(frames_rec, pic_height, pic_width, level):
+def picture_hashes(frames_rec, pic_height, pic_width, level, bitdepth=8):
     """CRC-32 of reconstructed (padded, float) pictures, taken on the device in ONE ops.crc32 call for all of them.
     -> per frame {"y", "cb", "cr": of the cropped, rounded planes as frames_to_u8 writes them (ops.planes_to_u8), "frame":
     of the three in file order (crc32_combine), the CRC-32 of the frame's bytes in the .yuv}; level "f32" adds "y_f32" and
-    "c_f32", of the padded float32 luma and chroma tensors as stored, the stricter check."""
+    "c_f32", of the padded float32 luma and chroma tensors as stored, the stricter check.
+    bitdepth=9..16: the integer planes are the 16-bit ones of frames_to_u16 (ops.planes_to_u16), hashed as their
+    little-endian bytes go to the file; the levels are then "u16" (the keys of "u8") and "f32"."""
     from pMCTF.hip import ops
-    if level not in HASH_LEVELS:
-        raise ValueError(f"level is one of {HASH_LEVELS} (got {level!r})")
+    bitdepth = check_bitdepth(bitdepth)
+    check_hash_level(level, bitdepth)
     hc, wc = pic_height // 2, pic_width // 2
     per_frame = len(HASH_KEYS[level]) - 1
+    sample_bytes = 2 if bitdepth > 8 else 1
     tensors = []
     for rec_y, rec_c, _ in frames_rec:
         y, c = rec_y.contiguous(), rec_c.contiguous()
-        c8 = ops.planes_to_u8(c, hc, wc)
-        tensors += [ops.planes_to_u8(y, pic_height, pic_width), c8[0], c8[1]]
+        if bitdepth > 8:
+            c8 = ops.planes_to_u16(c, hc, wc, bitdepth)
+            tensors += [ops.planes_to_u16(y, pic_height, pic_width, bitdepth), c8[0], c8[1]]
+        else:
+            c8 = ops.planes_to_u8(c, hc, wc)
+            tensors += [ops.planes_to_u8(y, pic_height, pic_width), c8[0], c8[1]]
         if level == "f32":
             tensors += [y, c]
     crcs = ops.crc32(tensors)
@@ -791,7 +929,7 @@ def picture_hashes(frames_rec, pic_height, pic_width, level):
     for i in range(len(frames_rec)):
         v = crcs[i * per_frame:(i + 1) * per_frame]
         rec = {"y": v[0], "cb": v[1], "cr": v[2],
-               "frame": crc32_combine(crc32_combine(v[0], v[1], hc * wc), v[2], hc * wc)}
+               "frame": crc32_combine(crc32_combine(v[0], v[1], hc * wc * sample_bytes), v[2], hc * wc * sample_bytes)}
         if level == "f32":
             rec.update(y_f32=v[3], c_f32=v[4])
         out.append(rec)
@@ -873,12 +1011,14 @@ def compare_hash_records(decoded, recorded, first_frame=0, **where):
 
 def check_yuv_hashes(bin_folder, yuv_path):
     """A decoded planar 4:2:0 file against bin_folder's picture_hashes.json at the u8 level, on the host with zlib alone
-    -> (frames checked, mismatches as compare_hash_records lists them).  ValueError for a file of the wrong length."""
+    -> (frames checked, mismatches as compare_hash_records lists them).  ValueError for a file of the wrong length.
+    A folder with a picture_format.json holds pictures of 16-bit samples: two bytes each, the u16 level."""
     import zlib
     header = read_sequence_header(bin_folder)
+    sample_bytes = 2 if read_picture_format(bin_folder) > 8 else 1
     recorded = read_picture_hashes(bin_folder, header["frame_num"])["frames"]
     h, w = header["height"], header["width"]
-    ny, nc = h * w, (h // 2) * (w // 2)
+    ny, nc = h * w * sample_bytes, (h // 2) * (w // 2) * sample_bytes
     if os.path.getsize(yuv_path) != header["frame_num"] * (ny + 2 * nc):
         raise ValueError(f"{yuv_path}: {os.path.getsize(yuv_path)} bytes, {header['frame_num']} pictures of {w}x{h} have "
                          f"{header['frame_num'] * (ny + 2 * nc)}")
@@ -900,8 +1040,10 @@ def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
     yuv_out may then be None (PNGs only).
     A folder that holds picture hashes (encode_sequence(picture_hash=...)) is checked against them:
     decode_sequence_checked with verify="auto", which also has the other modes.  Its parameters stay these five.
+    A folder with a picture_format.json (encode_sequence(bitdepth=9..16)) is written as little-endian 16-bit samples of
+    that depth (frames_to_u16); png_out is then refused (ValueError).
     Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP, "verified": pictures checked,
-    "hash_mismatches": []}."""
+    "hash_mismatches": [], "bitdepth"}."""
     return decode_sequence_checked(codec, bin_folder, yuv_out, device, png_out, verify="auto")
 
 
@@ -921,6 +1063,10 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     if yuv_out is None and png_out is None:
         raise ValueError("nothing to write: give yuv_out, png_out or both")
     header = read_sequence_header(bin_folder)
+    bitdepth = read_picture_format(bin_folder)
+    if bitdepth > 8 and png_out is not None:
+        raise ValueError(f"{os.path.join(bin_folder, PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
+                         f"8-bit PNGs; decode to a .yuv")
     check_sequence_header(header, codec_header_fields(codec))
     dev = codec.engine().dev
     if device is not None and torch.device(device).type != dev.type:
@@ -939,18 +1085,21 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
                                    ll_order=header["ll_order"])
             if recorded is not None:
                 first = k * header["gop"]
-                bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"]),
+                bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"], bitdepth),
                                            recorded["frames"][first:first + header["gop"]], first, gop=k, folder=folder)
                 if bad and verify != "report":
                     raise PictureHashMismatch(bad[0])
                 mismatches += bad
                 verified += header["gop"]
             if f is not None:
-                for planes in frames_to_u8(out["frames"], h, w):
+                pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
+                    frames_to_u8(out["frames"], h, w)
+                for planes in pictures:
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:
                 write_pngs(png_out, k * header["gop"], frames_to_rgb8(out["frames"], h, w))
             shapes += [(h, w)] * header["gop"]
             seconds.append(time.time() - t0)
-    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches}
+    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
+            "bitdepth": bitdepth}

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Check a decoded planar 8-bit 4:2:0 file against the picture hashes its encoder recorded, on the CPU with zlib alone.
+"""Check a decoded planar 4:2:0 file against the picture hashes its encoder recorded, on the CPU with zlib alone.
 
     python tools/check_picture_hashes.py BIN_FOLDER DECODED.yuv
 
 BIN_FOLDER was written by tools/encode_sequence.py --picture-hash u8|f32 (sequence.json and picture_hashes.json); the
 check is at the u8 level: the CRC-32 of every plane and of every whole frame of DECODED.yuv.  Prints the first mismatching
-frame and plane and exits with status 1 on a mismatch, with status 2 when the folder or the file cannot be checked."""
+frame and plane and exits with status 1 on a mismatch, with status 2 when the folder or the file cannot be checked.
+A folder coded above 8 bits (picture_format.json) is checked at the u16 level: two bytes per sample."""
 import argparse
 import os
 import sys

@@ -9,7 +9,9 @@ The number of motion stages comes from the folder's sequence.json; the weights m
 with.  The decoder refuses a header whose arithmetic profile (PMCTF_PRECISION) or ATen thread setting
 (PMCTF_ATEN_THREADS) differs from this process's.  A folder coded with --picture-hash holds the encoder's picture hashes:
 every decoded picture is checked against them (a mismatch stops the decoder before that GOP is written) unless --no-verify
-is given; --verify insists on the hashes being there, --verify-report writes everything and lists the mismatches."""
+is given; --verify insists on the hashes being there, --verify-report writes everything and lists the mismatches.
+A folder coded with --bitdepth above 8 (it holds picture_format.json) is written as little-endian 16-bit samples of that
+depth; the depth found is printed with the summary."""
 import argparse
 import json
 import os
@@ -57,6 +59,7 @@ def main():
             sys.exit(f"picture hash mismatch: {e}")
     n = len(out["frames"])
     print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out, "png": a.png,
+                      "bitdepth": out["bitdepth"],
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
                       "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"])}))
     for m in out["hash_mismatches"]:

@@ -9,7 +9,8 @@ SOURCE is a planar 8-bit 4:2:0 file (--width and --height required) or a folder 
 order and converted to 4:2:0 on the GPU (their size is read from the files).  tools/decode_sequence.py reads BIN_FOLDER
 back with the same weights.  --picture-hash u8|f32 also records the CRC-32 of every reconstructed picture
 (BIN_FOLDER/picture_hashes.json), which the decoder then checks; tools/check_picture_hashes.py checks a decoded .yuv against
-it without a GPU."""
+it without a GPU.  --bitdepth B (9..16): SOURCE.yuv holds little-endian 16-bit samples of that depth (yuv420p10le and its
+like); BIN_FOLDER/picture_format.json tells the decoder, which writes the same layout back; --picture-hash is then u16|f32."""
 import argparse
 import os
 import sys
@@ -32,8 +33,10 @@ def main():
     ap.add_argument("--height", type=int, help="picture height (.yuv sources)")
     ap.add_argument("--decoded-frames", metavar="DIR", help="save every reconstructed frame there as {index}.png")
     ap.add_argument("--msssim", action="store_true", help="fill the MS-SSIM fields of the record (GPU quality kernels)")
-    ap.add_argument("--picture-hash", choices=("u8", "f32"),
-                    help="record picture hashes: of the written 8-bit planes (u8), and of the padded float32 reconstructions (f32)")
+    ap.add_argument("--picture-hash", choices=("u8", "u16", "f32"),
+                    help="record picture hashes: of the written planes (u8; u16 with --bitdepth above 8), and of the padded "
+                         "float32 reconstructions (f32)")
+    ap.add_argument("--bitdepth", type=int, default=8, help="bit depth of a .yuv source: 8, or 9..16 for 16-bit samples")
     ap.add_argument("source", help=".yuv file or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args()
@@ -42,6 +45,9 @@ def main():
     from pMCTF.models.video.pMCTF_L import pMCTF
     try:
         pmctf_gop.gop_pairs(a.gop)
+        pmctf_gop.check_bitdepth(a.bitdepth)
+        if a.picture_hash is not None:
+            pmctf_gop.check_hash_level(a.picture_hash, a.bitdepth)
     except ValueError as e:
         ap.error(str(e))
     if os.path.isdir(a.source):
@@ -53,7 +59,8 @@ def main():
         if a.width is None or a.height is None:
             ap.error("--width and --height are required for a .yuv source")
         src_format, width, height = "yuv", a.width, a.height
-        available = os.path.getsize(a.source) // (width * height + 2 * (width // 2) * (height // 2))
+        sample_bytes = 2 if a.bitdepth > 8 else 1
+        available = os.path.getsize(a.source) // ((width * height + 2 * (width // 2) * (height // 2)) * sample_bytes)
     frames = a.frames if a.frames is not None else available // a.gop * a.gop
     if frames <= 0 or frames % a.gop or frames > available:
         ap.error(f"{frames} frames: need a positive multiple of the GOP length {a.gop}, at most the {available} of the source")
@@ -70,7 +77,7 @@ def main():
     with torch.no_grad():
         out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
                                         src_format=src_format, decoded_frame_path=a.decoded_frames, keep_gops=True,
-                                        msssim=a.msssim, picture_hash=a.picture_hash)
+                                        msssim=a.msssim, picture_hash=a.picture_hash, bitdepth=a.bitdepth)
     print(out["json"])
 
 

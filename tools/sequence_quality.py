@@ -4,7 +4,9 @@
     python tools/sequence_quality.py SRC.yuv REC.yuv --width 1920 --height 1080 [--frames N] [--json out.json]
 
 One line per frame in the evaluation script's wording, then the averages.  With tools/decode_sequence.py this closes the
-loop  bitstream folder -> .yuv -> quality.  The metrics run on the GPU (pmctf_gop.sequence_quality)."""
+loop  bitstream folder -> .yuv -> quality.  The metrics run on the GPU (pmctf_gop.sequence_quality).  --bitdepth B (9..16):
+both files hold little-endian 16-bit samples of that depth; the PSNRs are against 2^B - 1, RGB-PSNR and MS-SSIM (defined
+on 8-bit RGB) are reported as 0."""
 import argparse
 import json
 import os
@@ -24,17 +26,20 @@ def main():
     ap.add_argument("--gop", type=int, help="GOP length, to label the frame types as encode_sequence does")
     ap.add_argument("--no-msssim", action="store_true", help="PSNR only")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--bitdepth", type=int, default=8, help="bit depth of both files: 8, or 9..16 for 16-bit samples")
     ap.add_argument("--json", help="write the per-frame tables and their means here")
     a = ap.parse_args()
     if a.width <= 0 or a.height <= 0 or (a.width | a.height) & 1:
         ap.error("width and height must be even and positive")
-    frame_bytes = a.width * a.height + 2 * (a.width // 2) * (a.height // 2)
+    if a.bitdepth != 8 and not 9 <= a.bitdepth <= 16:
+        ap.error("bitdepth is 8 or 9..16")
+    frame_bytes = (a.width * a.height + 2 * (a.width // 2) * (a.height // 2)) * (2 if a.bitdepth > 8 else 1)
     n = a.frames if a.frames is not None else min(os.path.getsize(p) for p in (a.src_yuv, a.rec_yuv)) // frame_bytes
     if n <= 0:
         ap.error("no complete picture to compare")
     import pmctf_gop
     out = pmctf_gop.sequence_quality(a.src_yuv, a.rec_yuv, a.width, a.height, n, a.device, gop=a.gop,
-                                     msssim=not a.no_msssim)
+                                     msssim=not a.no_msssim, bitdepth=a.bitdepth)
     for line in out["lines"]:
         print(line)
     m = out["mean"]
