@@ -475,6 +475,22 @@ int pmctf_frame_sse_u16_f32(const float *rec_y, const float *rec_c, const float 
                             int h, int w, int bitdepth, uint64_t *sse3, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Sequence structure pre-analysis (csrc/scene_ops.hip): the luma histogram of one picture and its sum of absolute
+ * differences against the previous one, the figures pmctf_seq.scene_cuts decides scene changes from.
+ *
+ * pmctf_luma_activity_f32: cur, prev: dense un-padded luma originals (1,1,h,w) as pmctf_yuv420_u8_to_planes_f32 /
+ *   pmctf_yuv420_u16_to_planes_f32 return them (a sample v is v * 2^-s, s = bitdepth - 8), 16-byte aligned; prev may be
+ *   null.  Per element u = rint(clamp(x * 2^s, 0, 65535)) as an integer (exact for every original; NaN -> 0);
+ *   hist256[min(u >> s, 255)] += 1 over cur (256 values on the device, 4-byte aligned) and, unless prev is null,
+ *   *sad = sum |u_cur - u_prev| (one value on the device, 8-byte aligned; with a null prev it is not touched and may be
+ *   null).  bitdepth 8..16; any h, w in 1..16384.  Integer atomic adds only (LDS, then one per workgroup and non-zero
+ *   bin, one 64-bit one per workgroup for the SAD): exact and the same on every run.  One clear per output and one
+ *   launch, no synchronisation.  PMCTF_EINVAL, before anything is enqueued, for a null cur or hist256, a null sad with a
+ *   prev, a bitdepth or a size out of range and a pointer less aligned than stated. */
+int pmctf_luma_activity_f32(const float *cur, const float *prev, int h, int w, int bitdepth, uint32_t *hist256,
+                            uint64_t *sad, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Picture hashes (csrc/picture_hash.hip): crc_out[s] = CRC-32 of the bytes [data, data + bytes) of segs[s], s < n_segs, as
  * zlib.crc32 computes it (reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF).  The encoder records
  * the hashes of its reconstructed pictures, the decoder recomputes and compares them (pmctf_gop.picture_hashes).

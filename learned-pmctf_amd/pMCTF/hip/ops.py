@@ -770,6 +770,53 @@ def frame_sse_hbd(rec_y, rec_c, org_y, org_c, h, w, bitdepth):
     return res
 
 
+# ------------------------------------------------------------------------------------------------
+# sequence structure pre-analysis (csrc/scene_ops.hip)
+def luma_activity(cur, prev, bitdepth=8, hist=None, sad=None):
+    """The luma histogram of one picture and its sum of absolute differences against the previous one, in integers at
+    `bitdepth` 8..16 bits (pmctf_luma_activity_f32).  cur, prev: un-padded luma originals (1,1,h,w) float32 as
+    planes_from_u8 / planes_from_u16 return them; prev may be None.
+    -> (hist: 256 int32 counts of min(v >> (bitdepth - 8), 255), sad: one int64 or None without a prev), device tensors;
+    nothing is copied to the host.  hist / sad: caller-supplied outputs (a contiguous int32 slice of 256 values, a
+    contiguous int64 slice of one), so that a run of pictures is read back with one copy.  One launch and its clears."""
+    b = int(bitdepth)
+    if not 8 <= b <= HBD_MAX:
+        raise ValueError(f"bitdepth is 8..{HBD_MAX} (got {bitdepth})")
+    for t in (cur,) if prev is None else (cur, prev):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("expect float32 tensors")
+    if cur.dim() < 2 or cur.numel() != cur.shape[-2] * cur.shape[-1]:
+        raise ValueError(f"expect one luma plane (1,1,h,w), got {tuple(cur.shape)}")
+    h, w = int(cur.shape[-2]), int(cur.shape[-1])
+    if not (1 <= h <= PICTURE_MAX_SIDE and 1 <= w <= PICTURE_MAX_SIDE):
+        raise ValueError(f"plane sides are 1..{PICTURE_MAX_SIDE} (got {h}x{w})")
+    if prev is not None and tuple(prev.shape) != tuple(cur.shape):
+        raise ValueError(f"the previous picture is {tuple(prev.shape)}, this one {tuple(cur.shape)}")
+    dev = _dev(cur)
+    cur = cur.contiguous()
+    if prev is not None:
+        _dev(prev)
+        prev = prev.contiguous()
+    if hist is None:
+        hist = torch.empty(256, dtype=torch.int32, device=dev)
+    elif not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int32 and hist.is_contiguous()
+              and hist.numel() == 256):
+        raise ValueError("hist: a contiguous int32 device tensor of 256 values")
+    if prev is None:
+        if sad is not None:
+            raise ValueError("sad: there is no sum without a previous picture")
+    elif sad is None:
+        sad = torch.empty(1, dtype=torch.int64, device=dev)
+    elif not (isinstance(sad, torch.Tensor) and sad.is_cuda and sad.dtype == torch.int64 and sad.is_contiguous()
+              and sad.numel() == 1):
+        raise ValueError("sad: a contiguous int64 device tensor of one value")
+    _lib.check(_lib.hip().pmctf_luma_activity_f32(_p(cur), None if prev is None else _p(prev), h, w, b,
+                                                  C.c_void_p(hist.data_ptr()),
+                                                  None if sad is None else C.c_void_p(sad.data_ptr()), _stream()),
+               "luma_activity")
+    return hist, sad
+
+
 CRC32_TILE_BYTES = 4096                   # PMCTF_CRC32_TILE_BYTES of include/pmctf_hip.h
 CRC32_MAX_SEGMENTS = 65535
 

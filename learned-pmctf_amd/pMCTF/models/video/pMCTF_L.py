@@ -606,6 +606,44 @@ class pMCTF(nn.Module):
 
     @torch.no_grad()
     @_gated
+    def encode_lone_picture(self, frame, output_folder, pic_width, pic_height, psize=128, skip_decoding=True, q_index=0):
+        """A picture with no partner (a GOP of one, pmctf_seq): frame = [Y (1,1,Hp,Wp), UV (2,1,Hp/2,Wp/2)] padded planes,
+        coded by the L coder alone exactly as the L picture of a pair is (no motion, no temporal lifting, no H file).
+        Writes output_folder/0_main.bin and 0_C_main.bin with the framing of every other L picture; with
+        skip_decoding=False the LL symbols are in the sequential decoder's order and the returned planes are decoded from
+        the files, as in encode_one_stage.
+        -> {"L_t", "L_tc": reconstructed planes, "bit_L": 8 x both files' bytes, "bit_Lc": the chroma file's share,
+            "encoding_time", "decoding_time"}"""
+        self.flush()
+        y, c = unwrap(list(frame))
+        eng = self.engine()
+        start = time.time()
+        paths = {False: osp.join(output_folder, "0_main.bin"), True: osp.join(output_folder, "0_C_main.bin")}
+        headers = {False: lambda n: image_header(pic_height, pic_width, 1, n),
+                   True: lambda n: image_header(pic_height // 2, pic_width // 2, 2, n)}
+        jobs, synth = {}, {}
+        for chroma, planes in ((False, y), (True, c)):
+            synth[chroma], stream = eng.pwave_compress("lp_coder", planes.contiguous().float(), q_index, None,
+                                                       not skip_decoding, defer=True)
+            jobs[chroma] = eng.coder.submit(stream, eng.tables, headers[chroma], paths[chroma], eng.keep_streams)
+        rec = {chroma: fn() for chroma, fn in synth.items()}
+        bits = {chroma: j.result()[0] * 8.0 for chroma, j in jobs.items()}
+        encoding_time = time.time() - start
+        decoding_time = 0
+        if not skip_decoding:
+            t0 = time.time()
+            files = []
+            for chroma in (False, True):
+                with open(paths[chroma], "rb") as f:
+                    files.append((f.read(), chroma, True, 0))
+            rec[False], rec[True] = self.decompress_gop_files(files, psize=psize, q_index=q_index, ll_order="position")
+            torch.cuda.synchronize()
+            decoding_time = time.time() - t0
+        return {"L_t": rec[False], "L_tc": rec[True], "bit_L": bits[False] + bits[True], "bit_Lc": bits[True],
+                "encoding_time": encoding_time, "decoding_time": decoding_time}
+
+    @torch.no_grad()
+    @_gated
     def forward_one_stage(self, ref_frame, cur_frame, q_index, code_lt, dpb, mv_hat=None, stage_idx=0, me_downsample=1):
         """Estimate-mode stage (pMCTF_L.py:332-379): the same networks as encode_one_stage with Laplace / factorized
         bit estimates instead of range coding.  ref_frame / cur_frame are (N,1,H,W) planes (Y, or UV with the luma

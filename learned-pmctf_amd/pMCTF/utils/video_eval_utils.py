@@ -86,7 +86,8 @@ def generate_log_json(frame_num, frame_types, bits, bpp_mv, psnrs, rgb_psnrs, ss
             log.update({"ave_p_frame_bpp": 0, "ave_p_frame_psnr": 0, "ave_p_frame_psnr_rgb": 0,
                         "ave_p_frame_msssim": 0})
     log["ave_all_frame_bpp"] = (i["bit"] + p["bit"] + b["bit"]) / (frame_num * frame_pixel_num)
-    log["ave_all_frame_bpp_mv"] = (p["mv"] + b["mv"]) / (p["n"] + b["n"])
+    # a sequence of lone pictures only (pmctf_seq) has no frame with motion: 0, as the ave_p_* fields above
+    log["ave_all_frame_bpp_mv"] = (p["mv"] + b["mv"]) / (p["n"] + b["n"]) if p["n"] + b["n"] else 0
     log["ave_all_frame_psnr"] = (i["psnr"] + p["psnr"] + b["psnr"]) / frame_num
     log["ave_all_frame_psnr_rgb"] = (i["rgb"] + p["rgb"] + b["rgb"]) / frame_num
     log["ave_all_frame_msssim"] = (i["ssim"] + p["ssim"] + b["ssim"]) / frame_num

@@ -407,6 +407,33 @@ def rgb_psnr(rec_y, rec_c, y, c):
     return psnr(to_rgb(y, c), to_rgb(rec_y, rec_c))
 
 
+def report_gop(rec, orig, h, w, bits, bits_mv, first_frame, tables, ssims, hashes, picture_hash=None, bitdepth=8,
+               decoded_frame_path=None, msssim=False):
+    """What a sequence driver does with one reconstructed GOP (encode_sequence, pmctf_seq.encode_sequence_gops): the
+    picture hashes, the saved PNGs, the quality functions and the per-frame tables, appended in place.  rec: the pictures
+    decode_gop returned (a lone picture: its one reconstruction), orig: the un-padded originals."""
+    if picture_hash is not None:
+        hashes += picture_hashes(rec, h, w, picture_hash, bitdepth)
+    if decoded_frame_path is not None:
+        write_pngs(decoded_frame_path, first_frame, frames_to_rgb8(rec, h, w))
+    if bitdepth > 8:
+        quality = gop_quality_hbd(rec, orig, h, w, bitdepth)
+    else:
+        quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
+    tables["bits"] += bits
+    tables["bpp_mv"] += [b / (h * w) for b in bits_mv]
+    tables["psnr"] += [p["yuv"] for p in quality]
+    tables["frame_types"] += [0] + [1] * (len(rec) - 1)         # the one coded L picture of a GOP, then its H pictures
+    if msssim or bitdepth > 8:
+        tables["psnr_rgb"] += [p["rgb"] for p in quality]
+        ssims += [p["msssim"] for p in quality]
+        return
+    for (ry, rc, _), (y, c) in zip(rec, orig):
+        crop_y = torch.round(ry.clamp(0, 255.0))[:, :, :h, :w]
+        crop_c = torch.round(rc.clamp(0, 255.0))[:, :, :h // 2, :w // 2]
+        tables["psnr_rgb"].append(rgb_psnr(crop_y, crop_c, y, c))
+
+
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
                     skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
                     picture_hash=None, bitdepth=8, keep_gops=False, msssim=False):
@@ -490,26 +517,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
                     seconds[k] += r[k]
             lines += enc["log"]
             rec = decode_gop(codec, enc["frames_coded"])
-            if picture_hash is not None:
-                hashes += picture_hashes(rec, h, w, picture_hash, bitdepth)
-            if decoded_frame_path is not None:
-                write_pngs(decoded_frame_path, first_frame, frames_to_rgb8(rec, h, w))
-            if bitdepth > 8:
-                quality = gop_quality_hbd(rec, orig, h, w, bitdepth)
-            else:
-                quality = gop_quality(rec, orig, h, w, msssim=True) if msssim else gop_psnr(rec, orig, h, w)
-            tables["bits"] += enc["bits"]
-            tables["bpp_mv"] += [b / (h * w) for b in enc["bits_mv"]]
-            tables["psnr"] += [p["yuv"] for p in quality]
-            tables["frame_types"] += [0] + [1] * (gop - 1)          # the one coded L picture of a GOP, then its H pictures
-            if msssim or bitdepth > 8:
-                tables["psnr_rgb"] += [p["rgb"] for p in quality]
-                ssims += [p["msssim"] for p in quality]
-                continue
-            for (ry, rc, _), (y, c) in zip(rec, orig):
-                crop_y = torch.round(ry.clamp(0, 255.0))[:, :, :h, :w]
-                crop_c = torch.round(rc.clamp(0, 255.0))[:, :, :h // 2, :w // 2]
-                tables["psnr_rgb"].append(rgb_psnr(crop_y, crop_c, y, c))
+            report_gop(rec, orig, h, w, enc["bits"], enc["bits_mv"], first_frame, tables, ssims, hashes,
+                       picture_hash=picture_hash, bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
     reader.close()
     if keep_gops:
         write_sequence_header(bin_folder, width=width, height=height, frame_num=frame_num, gop=gop, q_index=q_index,
@@ -593,6 +602,22 @@ SEQUENCE_FORMAT_VERSION = 1
 SEQUENCE_FIELDS = ("width", "height", "frame_num", "gop", "q_index", "psize", "me_downsample", "num_me_stages", "ll_order",
                    "precision", "aten_threads")
 LL_ORDERS = ("position", "plane")
+
+
+GOP_STRUCTURE = "gop_structure.json"                  # the header of a structured folder (pmctf_seq), instead of sequence.json
+
+
+def sequence_layout(bin_folder):
+    """-> (header record, [(first, size, psize, me_downsample)] per GOP folder) of a folder written by encode_sequence
+    (keep_gops=True: sequence.json, equal GOPs) or by pmctf_seq.encode_sequence_gops (gop_structure.json: a list of GOPs).
+    ValueError as read_sequence_header / pmctf_seq.read_gop_structure raise it; a folder with both headers is refused."""
+    if os.path.exists(os.path.join(bin_folder, GOP_STRUCTURE)):
+        import pmctf_seq
+        header = pmctf_seq.read_gop_structure(bin_folder)
+        return header, [(g["first"], g["size"], g["psize"], g["me_downsample"]) for g in header["gops"]]
+    header = read_sequence_header(bin_folder)
+    gop = header["gop"]
+    return header, [(k * gop, gop, header["psize"], header["me_downsample"]) for k in range(header["frame_num"] // gop)]
 
 
 def gop_folder(k):
@@ -739,6 +764,7 @@ def _read_framed(path, header_bytes):
 def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize=128, me_downsample=1, ll_order="plane",
                      luma_stage0=False):
     """Decode one GOP from the files encode_gop wrote into bin_folder, with nothing else from the encoder.
+    gop=1: a lone picture of a structured sequence (pmctf_seq): 0_main.bin and 0_C_main.bin through the same batch.
     Every picture file of the GOP is started as ONE batch (their sequential LL parts side by side, batched per geometry:
     codec._decompress_gop_files_begin); under them the motion files are decoded stage by stage, pair by pair in coding
     order (the motion context restarts per stage, as in encode_gop; a reduced-resolution motion stream is decoded at the
@@ -751,8 +777,8 @@ def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psi
     import struct
     if ll_order not in LL_ORDERS:
         raise ValueError(f"ll_order must be one of {LL_ORDERS}")
-    pairs = gop_pairs(gop)
-    stages = pairs[-1][0] + 1
+    pairs = gop_pairs(gop) if gop != 1 else []          # a lone picture (pmctf_seq): its two L files, no motion, no synthesis
+    stages = pairs[-1][0] + 1 if pairs else 0
     pad_h = -(-pic_height // psize) * psize
     pad_w = -(-pic_width // psize) * psize
     files, names, slots = [], [], []
@@ -1014,7 +1040,7 @@ def check_yuv_hashes(bin_folder, yuv_path):
     -> (frames checked, mismatches as compare_hash_records lists them).  ValueError for a file of the wrong length.
     A folder with a picture_format.json holds pictures of 16-bit samples: two bytes each, the u16 level."""
     import zlib
-    header = read_sequence_header(bin_folder)
+    header, _ = sequence_layout(bin_folder)
     sample_bytes = 2 if read_picture_format(bin_folder) > 8 else 1
     recorded = read_picture_hashes(bin_folder, header["frame_num"])["frames"]
     h, w = header["height"], header["width"]
@@ -1042,6 +1068,8 @@ def decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None):
     decode_sequence_checked with verify="auto", which also has the other modes.  Its parameters stay these five.
     A folder with a picture_format.json (encode_sequence(bitdepth=9..16)) is written as little-endian 16-bit samples of
     that depth (frames_to_u16); png_out is then refused (ValueError).
+    A folder with a gop_structure.json instead of a sequence.json (pmctf_seq.encode_sequence_gops) is decoded GOP by GOP
+    with every GOP's own size, psize and me_downsample (sequence_layout); "header" is then the structure record.
     Returns {"header", "frames": [(height, width)] per written picture, "seconds": per GOP, "verified": pictures checked,
     "hash_mismatches": [], "bitdepth"}."""
     return decode_sequence_checked(codec, bin_folder, yuv_out, device, png_out, verify="auto")
@@ -1062,7 +1090,7 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
         raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
     if yuv_out is None and png_out is None:
         raise ValueError("nothing to write: give yuv_out, png_out or both")
-    header = read_sequence_header(bin_folder)
+    header, gops = sequence_layout(bin_folder)
     bitdepth = read_picture_format(bin_folder)
     if bitdepth > 8 and png_out is not None:
         raise ValueError(f"{os.path.join(bin_folder, PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
@@ -1077,20 +1105,18 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     h, w = header["height"], header["width"]
     shapes, seconds, mismatches, verified = [], [], [], 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
-        for k in range(header["frame_num"] // header["gop"]):
+        for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, gop_folder(k))
-            out = decode_gop_files(codec, folder, header["gop"], h, w, header["q_index"],
-                                   psize=header["psize"], me_downsample=header["me_downsample"],
+            out = decode_gop_files(codec, folder, size, h, w, header["q_index"], psize=psize, me_downsample=me_downsample,
                                    ll_order=header["ll_order"])
             if recorded is not None:
-                first = k * header["gop"]
                 bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"], bitdepth),
-                                           recorded["frames"][first:first + header["gop"]], first, gop=k, folder=folder)
+                                           recorded["frames"][first:first + size], first, gop=k, folder=folder)
                 if bad and verify != "report":
                     raise PictureHashMismatch(bad[0])
                 mismatches += bad
-                verified += header["gop"]
+                verified += size
             if f is not None:
                 pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
                     frames_to_u8(out["frames"], h, w)
@@ -1098,8 +1124,8 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:
-                write_pngs(png_out, k * header["gop"], frames_to_rgb8(out["frames"], h, w))
-            shapes += [(h, w)] * header["gop"]
+                write_pngs(png_out, first, frames_to_rgb8(out["frames"], h, w))
+            shapes += [(h, w)] * size
             seconds.append(time.time() - t0)
     return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
             "bitdepth": bitdepth}

@@ -3,7 +3,8 @@
 
     python tools/check_picture_hashes.py BIN_FOLDER DECODED.yuv
 
-BIN_FOLDER was written by tools/encode_sequence.py --picture-hash u8|f32 (sequence.json and picture_hashes.json); the
+BIN_FOLDER was written by tools/encode_sequence.py --picture-hash u8|f32 (sequence.json, or gop_structure.json with
+--structure, and picture_hashes.json); the
 check is at the u8 level: the CRC-32 of every plane and of every whole frame of DECODED.yuv.  Prints the first mismatching
 frame and plane and exits with status 1 on a mismatch, with status 2 when the folder or the file cannot be checked.
 A folder coded above 8 bits (picture_format.json) is checked at the u16 level: two bytes per sample."""

@@ -5,7 +5,8 @@
     python tools/decode_sequence.py --synth-seed 0 BIN_FOLDER OUT.yuv        (the deterministic synthetic weights)
     python tools/decode_sequence.py --synth-seed 0 --png DIR BIN_FOLDER      (RGB pictures DIR/{index}.png; OUT.yuv optional)
 
-The number of motion stages comes from the folder's sequence.json; the weights must be the ones the sequence was coded
+The number of motion stages comes from the folder's sequence.json (or gop_structure.json: a sequence coded with
+tools/encode_sequence.py --structure, whose GOPs have their own sizes); the weights must be the ones the sequence was coded
 with.  The decoder refuses a header whose arithmetic profile (PMCTF_PRECISION) or ATen thread setting
 (PMCTF_ATEN_THREADS) differs from this process's.  A folder coded with --picture-hash holds the encoder's picture hashes:
 every decoded picture is checked against them (a mismatch stops the decoder before that GOP is written) unless --no-verify
@@ -42,7 +43,7 @@ def main():
     import torch
     import pmctf_gop
     from pMCTF.models.video.pMCTF_L import pMCTF
-    header = pmctf_gop.read_sequence_header(a.bin_folder)
+    header, _ = pmctf_gop.sequence_layout(a.bin_folder)
     net = pMCTF(num_me_stages=header["num_me_stages"]).eval()
     if a.checkpoint is not None:
         from pMCTF.utils.stream_helper import get_state_dict

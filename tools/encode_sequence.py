@@ -10,7 +10,13 @@ order and converted to 4:2:0 on the GPU (their size is read from the files).  to
 back with the same weights.  --picture-hash u8|f32 also records the CRC-32 of every reconstructed picture
 (BIN_FOLDER/picture_hashes.json), which the decoder then checks; tools/check_picture_hashes.py checks a decoded .yuv against
 it without a GPU.  --bitdepth B (9..16): SOURCE.yuv holds little-endian 16-bit samples of that depth (yuv420p10le and its
-like); BIN_FOLDER/picture_format.json tells the decoder, which writes the same layout back; --picture-hash is then u16|f32."""
+like); BIN_FOLDER/picture_format.json tells the decoder, which writes the same layout back; --picture-hash is then u16|f32.
+--structure fill|scenecut|search (pmctf_seq.encode_sequence_gops; the default, fixed, is the call above): the sequence
+becomes a list of GOPs of 1, 2, 4, ... up to --gop pictures, so every picture of the source is coded (--frames defaults to
+all of them).  fill takes the largest GOP that still fits; scenecut first looks for scene changes (luma histogram and mean
+absolute difference on the GPU, thresholds --hd-min and --mad-min) and starts a GOP at each; search runs the reference's
+rate-distortion search per window of --gop pictures.  The chosen list and the cuts go to stderr; BIN_FOLDER then holds
+gop_structure.json instead of sequence.json, which tools/decode_sequence.py reads as well."""
 import argparse
 import os
 import sys
@@ -26,7 +32,12 @@ def main():
     w.add_argument("--synth-seed", type=int, help="deterministic synthetic weights (pmctf_synth) with this seed")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--num-me-stages", type=int, default=1, help="number of motion-estimation networks of the weights")
-    ap.add_argument("--gop", type=int, default=8, help="GOP length, a power of two")
+    ap.add_argument("--gop", type=int, default=8, help="GOP length, a power of two (the maximum with --structure)")
+    ap.add_argument("--structure", choices=("fixed", "fill", "scenecut", "search"), default="fixed",
+                    help="fixed: equal GOPs of --gop pictures (default); otherwise a list of GOPs up to --gop")
+    ap.add_argument("--hd-min", type=float, help="scenecut: least histogram change, 0..1 (default: pmctf_seq.HD_MIN)")
+    ap.add_argument("--mad-min", type=float,
+                    help="scenecut: least mean absolute luma difference, 8-bit units (default: pmctf_seq.MAD_MIN)")
     ap.add_argument("--q-index", type=int, default=3)
     ap.add_argument("--frames", type=int, help="pictures to code (default: all whole GOPs of the source)")
     ap.add_argument("--width", type=int, help="picture width (.yuv sources)")
@@ -61,9 +72,14 @@ def main():
         src_format, width, height = "yuv", a.width, a.height
         sample_bytes = 2 if a.bitdepth > 8 else 1
         available = os.path.getsize(a.source) // ((width * height + 2 * (width // 2) * (height // 2)) * sample_bytes)
-    frames = a.frames if a.frames is not None else available // a.gop * a.gop
-    if frames <= 0 or frames % a.gop or frames > available:
+    fixed = a.structure == "fixed"
+    frames = a.frames if a.frames is not None else (available // a.gop * a.gop if fixed else available)
+    if fixed and (frames <= 0 or frames % a.gop or frames > available):
         ap.error(f"{frames} frames: need a positive multiple of the GOP length {a.gop}, at most the {available} of the source")
+    if not fixed and not 0 < frames <= available:
+        ap.error(f"{frames} frames: need at least one, at most the {available} of the source")
+    if a.structure == "search" and a.gop < 4:
+        ap.error("--structure search needs --gop 4 or more")
     net = pMCTF(num_me_stages=a.num_me_stages).eval()
     if a.checkpoint is not None:
         from pMCTF.utils.stream_helper import get_state_dict
@@ -74,10 +90,23 @@ def main():
     net = net.to(a.device)
     net.update(force=True)
     os.makedirs(a.bin_folder, exist_ok=True)
+    common = dict(src_format=src_format, decoded_frame_path=a.decoded_frames, msssim=a.msssim, picture_hash=a.picture_hash,
+                  bitdepth=a.bitdepth)
     with torch.no_grad():
-        out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
-                                        src_format=src_format, decoded_frame_path=a.decoded_frames, keep_gops=True,
-                                        msssim=a.msssim, picture_hash=a.picture_hash, bitdepth=a.bitdepth)
+        if fixed:
+            out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+                                            keep_gops=True, **common)
+        else:
+            import pmctf_seq
+            out = pmctf_seq.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                                                 a.device, structure=a.structure,
+                                                 hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
+                                                 mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min, **common)
+            if "cuts" in out:
+                print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
+            print("GOPs (first picture: size, motion down-sampling): " +
+                  ", ".join(f"{g['first']}: {g['size']}" + (f" /{g['me_downsample']}" if g["me_downsample"] != 1 else "")
+                            for g in out["gops"]), file=sys.stderr)
     print(out["json"])
 
 
