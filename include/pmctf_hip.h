@@ -81,7 +81,9 @@ int64_t pmctf_conv2d_packed_bias_size(int Cout);
  * specialisations (wave-private and pipelined kernels, stride 1 and 2: no vector-ALU work in the tap loop), "K77" 0/1 the
  * 7x7 stride-1 pipelined kernel (8x32 and 4x16 tiles), "K33_SMALL" 0/1 the specialised 3x3 pipelined kernel with one cout
  * tile per workgroup on the cout-split planes the wave-private kernel does not take, "K11" 0/1 the flat GEMM kernel for 1x1 layers with at least "K11_MIN_TILES" (7) 16-cout tiles, "WAVE_SMALL" 0/1 the
- * wave-private kernel with one cout tile per workgroup on cout-split 3x3 planes that fill the waves' 4x16 tiles to >= 90 %.
+ * wave-private kernel with one cout tile per workgroup on cout-split 3x3 planes that fill the waves' 4x16 tiles to >= 90 %,
+ * "BSUM_TILEOUTER" 0/1 rule "blocks" 3x3 layers of 7 cout tiles on 8x32 tiles: one launch of the tile-outer kernel (1) or
+ * the 4 + 3 tiles in two launches of the wave-private kernel (0).
  * Environment only: PMCTF_FEWCOUT_LDS=0 / PMCTF_DWCONV_COLUMN=0 select the older one/two-cout and depthwise kernels. */
 int pmctf_conv2d_set_option(const char *name, long value);
 /* current value of a knob (-1: unknown name).  The launch plans of the drop-in path record their convolutions with

@@ -506,12 +506,10 @@ _Pragma("unroll")
 // alternate without copies, one copy per 16-channel chunk remains), every LDS address is ONE per-wave base register plus an
 // immediate, the staging slots' global offsets and bounds are computed once per tile, and the 16-channel chunk advances
 // a scalar base.  Same arithmetic and sum order as every other variant (chunk, ky, kx, ci ascending).
-// BSUM: summation rule "blocks" (per-chunk sums from zero, added in turn to a second accumulator set).  Two sets of
-// MT x 4 quads do not fit 256 registers at MT = 7: that instantiation runs ONE workgroup per CU (512 registers per lane, the
-// compiler keeps one set in AGPRs); the rule-0 instantiation measured the same 137 TFLOP/s at one workgroup per CU
-// (docs/history.md section 9), i.e. the kernel is MFMA-bound, not occupancy-bound.
+// BSUM: summation rule "blocks" (per-chunk sums from zero, added in turn to a second accumulator set `tot`), MT <= 4: two
+// sets of MT x 4 quads do not fit 256 registers at MT = 7 (conv3x3s1_blocks_tileouter_kernel below is that case).
 // MOFF >= 0: the workgroup takes MT cout tiles starting at tile MOFF of packed M-block blockIdx.z (a 7-tile block run as
-// 4 + 3 tiles in two launches: both accumulator sets of rule "blocks" then fit 256 registers at two workgroups per CU).
+// 4 + 3 tiles in two launches: the form the tile-outer kernel replaced, kept as the other arm of knob BSUM_TILEOUTER).
 template <int MT, int NBUF, bool BSUM, int MOFF>
 __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int tile, float *lds) {
     constexpr int NT = 4, LH = 6, LW = 18, MAXP = 7;
@@ -530,12 +528,9 @@ __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int
     float *wlds = lds + wave * NBUF * BUFSZ;
 
     // BSUM: `tot` starts as the bias and takes every chunk's sum when it is complete (S_0 + bias = bias + S_0 exactly).
-    // With 7 cout tiles the two sets are 224 registers: `tot` is pinned to the accumulation registers (AGPRs) by giving
-    // every access of it an "a" operand — left to itself the allocator keeps both sets in VGPRs and spills inside the loop.
-    constexpr bool TOT_AGPR = BSUM && MT >= 7;
+    static_assert(!BSUM || MT <= 4, "two accumulator sets of 7 tiles do not fit the register file");
     f32x4 acc[MT][NT];
-    f32x4 tot[BSUM && !TOT_AGPR ? MT : 1][BSUM && !TOT_AGPR ? NT : 1];
-    float tota[TOT_AGPR ? MT : 1][TOT_AGPR ? NT : 1][4];
+    f32x4 tot[BSUM ? MT : 1][BSUM ? NT : 1];
     {
         const float *bp = a.bp + (size_t)mtile0 * 16 + 4 * (lane >> 4);
 #pragma unroll
@@ -543,12 +538,7 @@ __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int
             const f32x4 b = *(const f32x4 *)(bp + mt * 16);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                if constexpr (TOT_AGPR) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) asm("v_accvgpr_write_b32 %0, %1" : "=a"(tota[mt][nt][e]) : "v"(b[e]));
-                } else if constexpr (BSUM) {
-                    tot[mt][nt] = b;
-                }
+                if constexpr (BSUM) tot[mt][nt] = b;
                 acc[mt][nt] = b;
             }
         }
@@ -661,19 +651,7 @@ __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    if constexpr (TOT_AGPR) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float t;
-                            asm("v_accvgpr_read_b32 %0, %1" : "=v"(t) : "a"(tota[mt][nt][e]));
-                            t = t + acc[mt][nt][e];
-                            asm("v_accvgpr_write_b32 %0, %1" : "=a"(tota[mt][nt][e]) : "v"(t));
-                        }
-                    } else {
-                        tot[mt][nt] = tot[mt][nt] + acc[mt][nt];
-                    }
-                }
+                for (int nt = 0; nt < NT; ++nt) tot[mt][nt] = tot[mt][nt] + acc[mt][nt];
         }
         // the other buffer was last read in chunk cb-1 by this same wave (NBUF = 1: this buffer, all of whose reads have
         // been issued by now): in-order LDS makes the overwrite safe
@@ -683,14 +661,7 @@ __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                if constexpr (TOT_AGPR) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) asm("v_accvgpr_read_b32 %0, %1" : "=v"(acc[mt][nt][e]) : "a"(tota[mt][nt][e]));
-                } else {
-                    acc[mt][nt] = tot[mt][nt];
-                }
-            }
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = tot[mt][nt];
     }
 
     PM_EPILOGUE_NOTRANS(a,
@@ -709,9 +680,192 @@ _Pragma("unroll")
 }
 
 template <int MT, int NBUF, bool BSUM = false, int MOFF = -1>
-__global__ __launch_bounds__(256, (BSUM && MT >= 7) ? 1 : (NBUF == 1 ? 3 : 2)) void conv3x3s1_wave_kernel(ConvArgs a) {
+__global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void conv3x3s1_wave_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     conv3x3s1_wave_body<MT, NBUF, BSUM, MOFF>(a, blockIdx.x, lds);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Summation rule "blocks" at 7 cout tiles in ONE launch: conv3x3s1_wave_kernel with the cout tile as the OUTER loop of a
+// chunk.  The chunk sums of different cout tiles are independent, so one tile at a time runs its whole 36-step chain
+// (9 taps x 4 k-steps, ky, kx, ci ascending, from the inline-zero C operand) into a set of four quads `acc`, which is
+// folded into the tile's running sums `tot[mt]` (they start as the bias: (bias + S_0) + S_1 + ..., the arithmetic of the
+// BSUM branch above) while the next tile runs into the other `acc` set.  Live accumulators are 112 + 2 x 16 registers
+// instead of 224, so all seven tiles fit two workgroups per CU and the patch is staged once per plane instead of once
+// per half.  The price is that the B operands are re-read from LDS for every tile (1008 ds_read_b32 per chunk and wave):
+// they are requested BAHEAD k-steps ahead of their use through a ring of register sets, and the weight fragments (one
+// per tile and tap, 16 MFMAs) WAHEAD taps ahead through a ring of WR sets.  Needs the 7-tile packed layout
+// (a.mtp == 7): a fragment's address is the M-block's buffer descriptor, a scalar offset and one lane offset.
+__global__ __launch_bounds__(256, 2) void conv3x3s1_blocks_tileouter_kernel(ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int MT = 7, NT = 4, LH = 6, LW = 18, MAXP = 7;
+    constexpr int BUFSZ = LH * LW * CP;
+    constexpr int E = LH * LW * 4;
+    // Measured on 1x576x960 / 8x576x960 (TFLOP/s): WR 4, BR 3: 121 / 143.6; WR 4, BR 4: 135 / 145.4; WR 6, BR 3: 135.4 /
+    // 145.8; WR 6, BR 4: 135.6 / 145.6; WR 4, BR 6: 135 / 145.1 — one of the two rings has to be deeper than the minimum.
+    constexpr int WR = 6, WAHEAD = WR - 1;          // weight-fragment ring
+    constexpr int BR = 3, BAHEAD = BR - 1;          // B-operand ring (252 k-steps per chunk: a multiple of 3)
+    constexpr int FOLD_AFTER = 2;                   // k-steps into the next tile at which a tile's sum is folded
+    constexpr int TSTEPS = MT * 9, KSTEPS = TSTEPS * 4;
+    constexpr unsigned WFRAG = 256 * 4, WTAP = MT * WFRAG, WCHUNK = 9 * WTAP;      // bytes
+    static_assert(KSTEPS % BR == 0, "the B ring must close over a chunk");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tile = blockIdx.x;
+    const int n = blockIdx.y;
+    const int mtile0 = blockIdx.z * MT;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const int oy0 = a.oy_base + ty * 8 + (wave >> 1) * 4, ox0 = tx * 32 + (wave & 1) * 16;
+    if (oy0 >= a.oy_end || ox0 >= a.Wo) return;          // this wave's 4x16 tile lies outside the plane (no barriers here)
+    const int iy0 = oy0 - a.pad_h, ix0 = ox0 - a.pad_w;
+    float *wlds = lds + wave * 2 * BUFSZ;
+
+    f32x4 tot[MT][NT];
+    {
+        const float *bp = a.bp + (size_t)mtile0 * 16 + 4 * (lane >> 4);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const f32x4 b = *(const f32x4 *)(bp + mt * 16);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) tot[mt][nt] = b;
+        }
+    }
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    // staging as in conv3x3s1_wave_body: lane owns float4 slots e = lane + 64*j of this wave's patch
+    bool ok[MAXP];
+    unsigned goff[MAXP];
+    f32x4 pre[MAXP];
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j) {
+        const int e = lane + 64 * j;
+        const int pix = e >> 2, part = e & 3;
+        const int ly = pix / LW, lx = pix - ly * LW;
+        const int gy = iy0 + ly, gx = ix0 + lx;
+        ok[j] = e < E && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+        goff[j] = ok[j] ? (unsigned)(((gy * a.W + gx) * a.Cin + part * 4) * 4) : 0u;
+        pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const char *xn = (const char *)(a.x + (size_t)n * a.H * a.W * a.Cin);
+    auto fetch = [&](int cb) {
+        const char *base = xn + cb * (CB * 4);
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j)
+            if (ok[j]) pre[j] = *(const f32x4 *)(base + goff[j]);
+    };
+    float *sdst = wlds + (lane >> 2) * CP + (lane & 3) * 4;
+    auto stash = [&](int buf) {
+        float *d0 = sdst + buf * BUFSZ;
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j) {
+            if (64 * j + 63 < E || lane + 64 * j < E) {
+                float2 *dst = (float2 *)(d0 + j * 16 * CP);
+                dst[0] = make_float2(pre[j].x, pre[j].y);
+                dst[1] = make_float2(pre[j].z, pre[j].w);
+            }
+        }
+    };
+    // weights: [cb][tap][mt][lane][ks] of this M-block; consumed in the order (cb, mt, tap).  Buffer loads: the
+    // descriptor of the M-block and a scalar offset per fragment (scalar ALU), ONE lane-offset register — as flat
+    // pointers the 63 fragment addresses of a chunk cost 18 register pairs and 36 vector adds per chunk.
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)((const char *)a.wp + (size_t)blockIdx.z * a.ncb * WCHUNK), 0, a.ncb * (int)WCHUNK, 0x00020000);
+    const int wl = lane * 16;
+    auto wload = [&](int soff) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, wl, soff, 0));
+    };
+    f32x4 wf[WR];
+#pragma unroll
+    for (int s = 0; s < WAHEAD; ++s) wf[s] = wload((s % 9) * WTAP + (s / 9) * WFRAG);
+    fetch(0);
+    stash(0);
+    const float *bl = wlds + (lane & 15) * CP + (lane >> 4);
+    float bq[BR][NT];
+    f32x4 acc[2][NT];               // the chunk sums of the tile in progress and of the one before it
+    for (int cb = 0; cb < a.ncb; ++cb) {
+        const float *cur = bl + (cb & 1) * BUFSZ;
+        const bool more = cb + 1 < a.ncb;
+        const int wc = cb * (int)WCHUNK;
+        const int wcn = more ? wc + (int)WCHUNK : wc;    // fragments past the last chunk re-read this chunk's: no branch
+#pragma unroll
+        for (int q = 0; q < BAHEAD; ++q)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                bq[q][nt] = cur[nt * LW * CP + (((q / 4) / 3) * LW + (q / 4) % 3) * CP + (q % 4) * 4];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int s = mt * 9 + t;
+                {   // the fragment of WAHEAD steps on, into the ring slot the previous step has just released
+                    const int sn = (s + WAHEAD) % TSTEPS;
+                    wf[(s + WAHEAD) % WR] = wload((s + WAHEAD < TSTEPS ? wc : wcn) + (sn % 9) * WTAP + (sn / 9) * WFRAG);
+                }
+                // Vector-memory loads return in order: the next chunk's patch (HBM) is requested right behind a weight
+                // fragment that is needed WAHEAD taps later, the deepest point of the ring.
+                if (s == 0 && more) fetch(cb + 1);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const int q = s * 4 + ks, qn = q + BAHEAD;
+                    if (qn < KSTEPS) {      // the next tile re-reads the same patch: the ring runs on across the tiles
+                        const int tn = (qn / 4) % 9, ksn = qn % 4;
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+                            bq[qn % BR][nt] = cur[nt * LW * CP + ((tn / 3) * LW + tn % 3) * CP + ksn * 4];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        acc[mt & 1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s % WR][ks], bq[q % BR][nt],
+                                                                               (t == 0 && ks == 0) ? zero4 : acc[mt & 1][nt], 0, 0, 0);
+                    // The previous tile's chunk sum is folded here, FOLD_AFTER k-steps into this tile: its last MFMAs
+                    // have left the pipe by now, so the adds do not wait for them.  The empty asm pins the fold: left
+                    // alone, the optimiser sinks all seven folds below the chunk's last MFMA, which keeps seven `acc`
+                    // sets alive (256 registers, 130 spilled).
+                    if (mt > 0 && t == 0 && ks == FOLD_AFTER - 1) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) {
+                            tot[mt - 1][nt] = tot[mt - 1][nt] + acc[(mt - 1) & 1][nt];
+                            asm volatile("" : "+v"(tot[mt - 1][nt]));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {       // the last tile's
+            tot[MT - 1][nt] = tot[MT - 1][nt] + acc[(MT - 1) & 1][nt];
+            asm volatile("" : "+v"(tot[MT - 1][nt]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // 63 steps per chunk: rotate the ring so that the next chunk's step 0 is in slot 0 again
+        {
+            f32x4 r[WR];
+#pragma unroll
+            for (int i = 0; i < WR; ++i) r[i] = wf[(i + TSTEPS) % WR];
+#pragma unroll
+            for (int i = 0; i < WR; ++i) wf[i] = r[i];
+        }
+        // the other buffer was last read in chunk cb-1 by this same wave: in-order LDS makes the overwrite safe
+        if (more) stash((cb + 1) & 1);
+    }
+
+    PM_EPILOGUE_NOTRANS(a,
+_Pragma("unroll")
+    for (int nt = 0; nt < NT; ++nt) {
+        const int oy = oy0 + nt, ox = ox0 + (lane & 15);
+        if (oy >= a.oy_end || ox >= a.Wo) continue;
+        const size_t pbase = (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.Cout;
+_Pragma("unroll")
+        for (int mt = 0; mt < MT; ++mt) {
+            const int co = (mtile0 + mt) * 16 + 4 * (lane >> 4);
+            if (co >= a.Cout) continue;
+            store_frag<ACT, RES>(a, tot[mt][nt], pbase, co);
+        }
+    })
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1578,7 +1732,7 @@ void choose_mt(int Cout, int &MT, int &MB) {
 // Tuning knobs: environment variable PMCTF_CONV_<NAME> at first use, or pmctf_conv2d_set_option("<NAME>", v).
 struct Knob { const char *name; long value; bool set; };
 Knob g_knobs[] = {{"WAVE", 1, false}, {"NT", 0, false}, {"MSPLIT_PX", 70000, false}, {"SPLIT", 1, false},
-                  {"BIGPX", 131072, false}, {"RES", 0, false}, {"MSPLIT_NT", 1, false}, {"C16", 1, false}, {"C16_WGS", 512, false}, {"C16_OCC", 2, false}, {"V1", 0, false}, {"V2", 0, false}, {"NBUF1", 1, false}, {"K33", 1, false}, {"WAVE_SMALL", 1, false}, {"K11", 1, false}, {"K77", 1, false}, {"K33_SMALL", 1, false}, {"K11_MIN_TILES", 7, false}, {"BIGPX_NOSPLIT", 200000, false}, {"BSUM_SPLIT", 1, false}};
+                  {"BIGPX", 131072, false}, {"RES", 0, false}, {"MSPLIT_NT", 1, false}, {"C16", 1, false}, {"C16_WGS", 512, false}, {"C16_OCC", 2, false}, {"V1", 0, false}, {"V2", 0, false}, {"NBUF1", 1, false}, {"K33", 1, false}, {"WAVE_SMALL", 1, false}, {"K11", 1, false}, {"K77", 1, false}, {"K33_SMALL", 1, false}, {"K11_MIN_TILES", 7, false}, {"BIGPX_NOSPLIT", 200000, false}, {"BSUM_TILEOUTER", 1, false}};
 std::once_flag g_knobs_once;
 inline long knob(const char *name) {
     // one-time, thread-safe read of the environment (ctypes callers may launch from several host threads)
@@ -1667,13 +1821,17 @@ int launch(const ConvArgs &a, int gz, hipStream_t st, int r0, int r1) {
         const bool plain_blocks = sc.bchunks == 1 && !sc.bias_first && a.act <= pm::ACT_LEAKY && a.KH == 3 && a.KW == 3 &&
                                   knob("K33") != 0 && (size_t)a.H * a.W * a.Cin * sizeof(float) < (1ull << 32);
         if constexpr (NT == 4 && TW16 == 2 && MT == 7) {
-            // 7 cout tiles as 4 + 3 in two launches (both accumulator sets in VGPRs, two workgroups per CU, the chunk sums
-            // folded with packed adds) instead of one launch with the running sums in AGPRs at one workgroup per CU.
-            // (Both halves in ONE kernel, a tile's halves adjacent on one XCD so that the second finds the patch in L2:
-            // measured 125 against 138 TFLOP/s — 246 registers and twice the code in one kernel.)
-            if (plain_blocks && a.S == 1 && wave_eligible(a) && knob("BSUM_SPLIT") != 0 && a.mtp == 7) {
+            // 7 cout tiles: two accumulator sets (224 registers) do not fit.  One launch of the tile-outer kernel (one tile's
+            // chunk sum at a time: 145.8 TFLOP/s steady state); knob BSUM_TILEOUTER = 0: 4 + 3 tiles in two launches of the
+            // wave kernel (both sets in VGPRs, the patch staged twice: 137.8).  (Both halves in ONE kernel, a tile's halves
+            // adjacent on one XCD: 125; the running sums in AGPRs at one workgroup per CU: 130.7.)
+            if (plain_blocks && a.S == 1 && wave_eligible(a) && a.mtp == 7) {
                 const int PH = 3 * a.S + a.KH, PW = 15 * a.S + a.KW;
                 const size_t wsmem = (size_t)PH * PW * CP * sizeof(float) * 2 * WAVES;
+                if (knob("BSUM_TILEOUTER") != 0) {
+                    CONV_LAUNCH(conv3x3s1_blocks_tileouter_kernel, grid, dim3(256), wsmem, st, b);
+                    return pm_launch_status();
+                }
                 static std::once_flag once_k4, once_k3;
                 allow_big_lds(conv3x3s1_wave_kernel<4, 2, true, 0>, once_k4);
                 allow_big_lds(conv3x3s1_wave_kernel<3, 2, true, 4>, once_k3);
@@ -1683,7 +1841,7 @@ int launch(const ConvArgs &a, int gz, hipStream_t st, int r0, int r1) {
                 return pm_launch_status();
             }
         }
-        if constexpr (NT == 4 && TW16 == 2 && (MT == 1 || MT == 2 || MT == 4 || MT == 7)) {
+        if constexpr (NT == 4 && TW16 == 2 && (MT == 1 || MT == 2 || MT == 4)) {
             if (plain_blocks && a.S == 1 && wave_eligible(a)) {
                 const int PH = 3 * a.S + a.KH, PW = 15 * a.S + a.KW;
                 constexpr int NB = MT <= 2 ? 1 : 2;       // narrow layers: single patch buffer, three workgroups per CU
