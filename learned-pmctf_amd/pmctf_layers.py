@@ -1,0 +1,489 @@
+"""Temporal layers: a coded sequence at 1/2^k of its frame rate, decoded from a subset of its files.
+
+Stage s of a GOP turns pairs of pictures into a low-band and a high-band picture and the next stage works on the low-band
+pictures alone (pmctf_gop.encode_gop), so a decoder that leaves out the high-band pictures of stages 0..k-1 and stops the
+synthesis after stage k holds the GOP's low-band pictures of level k: one picture per 2^k source pictures.  Nothing in
+the files has to change for that.  encode_gop names a pair's three files after its high-band picture, and both encode_gop
+and the decoder restart the motion context ({"mv_feature": None, "ref_mv_y": None}) at every stage, so the motion files
+of stage s decode without any file of an earlier stage.
+
+Level k >= 0; a GOP of size = 2^S pictures; kk = min(k, S): a GOP shallower than k gives its one low-band picture.
+  layer_times, layer_file_names, layer_bytes     the plan: which pictures come out, which files are read (pure Python)
+  decode_gop_files_layer, decode_sequence_layer  the decoder, on pmctf_gop's batched file decode and inverse_MCTF
+  write_layer_hashes, read_layer_hashes          layer_hashes.json: the CRC-32 of every layer picture, from a full decode
+  extract_layer                                  copies exactly the files of a level into a new folder (no codec, no GPU)
+motion_fill=True is the other classical use of the same picture files: the motion of the left-out stages is read as
+well, their high-band pictures are taken as zero and the whole synthesis runs, which gives every picture of the GOP.
+The plan, the hash record and extract_layer need no GPU; the decoders have no CPU path."""
+import json
+import os
+
+import pmctf_gop
+
+LAYER_HASHES = "layer_hashes.json"
+LAYER_HASH_FORMAT_VERSION = 1
+LAYER_EXTRACT = "layer_extract.json"
+LAYER_EXTRACT_VERSION = 1
+L_FILES = ("0_main.bin", "0_C_main.bin")
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_level(level):
+    """the temporal level as given: an integer >= 0; ValueError otherwise"""
+    if not _is_int(level) or level < 0:
+        raise ValueError(f"level is an integer, 0 or more (got {level!r})")
+    return level
+
+
+def gop_stages(gop):
+    """S of a GOP of 2^S pictures (0 for a lone picture); ValueError for a size that is not a power of two"""
+    if not _is_int(gop) or gop < 1 or gop & (gop - 1):
+        raise ValueError(f"the GOP length must be a power of two (got {gop!r})")
+    return gop.bit_length() - 1
+
+
+# --------------------------------------------------------------------------------------------------------------- the plan
+def layer_times(gops, level):
+    """[(gop index, source picture index)] of the pictures a level-`level` decode gives, in output order.  gops: the list
+    pmctf_gop.sequence_layout returns, [(first, size, ...)].  GOP (first, size = 2^S) yields first + j * 2^kk for
+    j < size >> kk, kk = min(level, S): a GOP shallower than the level yields its one low-band picture, a lone picture
+    itself, level 0 every picture."""
+    check_level(level)
+    out = []
+    for k, g in enumerate(gops):
+        first, size = g[0], g[1]
+        kk = min(level, gop_stages(size))
+        out += [(k, first + (j << kk)) for j in range(size >> kk)]
+    return out
+
+
+def layer_file_names(gop, level, motion_fill=False):
+    """the files a level-`level` decode of one GOP of `gop` pictures reads, in pmctf_gop.gop_file_names order: the three
+    files of every pair whose stage is >= kk, then 0_main.bin and 0_C_main.bin.  motion_fill: the {i}_mv.bin of the pairs
+    of stages < kk as well.  gop == 1: the two L files.  Level 0 is gop_file_names(gop); files(k) is a subset of
+    files(k - 1)."""
+    check_level(level)
+    kk = min(level, gop_stages(gop))
+    names = []
+    for stage, _, i_cur in (pmctf_gop.gop_pairs(gop) if gop != 1 else []):
+        if stage >= kk:
+            names += [f"{i_cur}.bin", f"{i_cur}_C_main.bin", f"{i_cur}_mv.bin"]
+        elif motion_fill:
+            names.append(f"{i_cur}_mv.bin")
+    return names + list(L_FILES)
+
+
+def layer_bytes(bin_folder, level, motion_fill=False):
+    """the rate of the layer: the sizes of exactly the files a level-`level` decode of the sequence in bin_folder reads,
+    summed over its GOPs.  ValueError naming a file that is missing."""
+    check_level(level)
+    _, gops = pmctf_gop.sequence_layout(bin_folder)
+    total = 0
+    for k, g in enumerate(gops):
+        for name in layer_file_names(g[1], level, motion_fill):
+            path = os.path.join(bin_folder, pmctf_gop.gop_folder(k), name)
+            try:
+                total += os.path.getsize(path)
+            except FileNotFoundError:
+                raise ValueError(f"{path}: missing") from None
+    return total
+
+
+# ---------------------------------------------------------------------------------------------------------------- one GOP
+def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, kk,
+                    motion_fill):
+    """decode_gop_files up to the synthesis, on the files of layer_file_names alone -> (frames_coded with None where
+    nothing was read, names read, bytes read).  The header checks, the one picture batch and the motion loop under it are
+    those of pmctf_gop.decode_gop_files."""
+    import struct
+    import torch
+    pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
+    pad_h = -(-pic_height // psize) * psize
+    pad_w = -(-pic_width // psize) * psize
+    files, paths, slots, read = [], [], [], []
+    nbytes = 0
+
+    def picture(name, chroma, low, me_num, slot):
+        nonlocal nbytes
+        path = os.path.join(bin_folder, name)
+        data = pmctf_gop._read_framed(path, 16)
+        h, w, n = struct.unpack(">III", data[:12])
+        want = (pic_height // 2, pic_width // 2, 2) if chroma else (pic_height, pic_width, 1)
+        if (h, w, n) != want:
+            raise ValueError(f"{path}: header says {n} plane(s) of {h}x{w}, expected {want[2]} of {want[0]}x{want[1]}")
+        files.append((data, chroma, low, me_num))
+        paths.append(path)
+        slots.append(slot)
+        read.append(name)
+        nbytes += len(data)
+
+    motion = []
+    for stage, _, i_cur in pairs:
+        if stage < kk and not motion_fill:
+            continue
+        me_num = min(codec.num_me_stages - 1, stage)
+        if stage >= kk:
+            picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
+            picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
+        path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
+        data = pmctf_gop._read_framed(path, 6)
+        motion.append((stage, i_cur, me_num, path, data[6:]))
+        read.append(f"{i_cur}_mv.bin")
+        nbytes += len(data)
+    picture(L_FILES[0], False, True, 0, (0, 0))
+    picture(L_FILES[1], True, True, 0, (0, 1))
+
+    begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, paths)
+    frames_coded = [[None, None, None] for _ in range(gop)]
+    dpb, at_stage = None, None
+    try:
+        for stage, i_cur, me_num, path, string in motion:
+            if stage != at_stage:                         # the context restarts per stage: what makes the layers independent
+                dpb, at_stage = {"mv_feature": None, "ref_mv_y": None}, stage
+            try:
+                d = codec.decompress_mv(string, torch.float32, pad_h // me_downsample, pad_w // me_downsample, dpb,
+                                        stage_idx=me_num, q_index=q_index, me_downsample=me_downsample)
+            except (ValueError, RuntimeError) as e:
+                raise ValueError(f"{path}: {e}") from e
+            frames_coded[i_cur][2] = d["mv_hat"]
+            dpb = {"mv_feature": d["mv_feature"], "ref_mv_y": d["mv_y_hat"]}
+    finally:
+        # the picture files are finished (and their threads and streams drained) whatever the motion files did
+        planes = codec._decompress_gop_files_end(begun)
+    for (i, c), plane in zip(slots, planes):
+        frames_coded[i][c] = plane
+    return frames_coded, read, nbytes
+
+
+def _synthesis(codec, frames_coded, stages, down_to, snapshots=None):
+    """pmctf_gop.decode_gop's loop for the stages `stages - 1` .. `down_to`, on the GOP's own stage numbers; modifies and
+    returns frames_coded.  snapshots: a dict that receives, per level k in down_to..stages, the low-band pictures of that
+    level ([Y, UV, None] at the indices j * 2^k) as the list holds them once stage k is undone."""
+    def keep(k):
+        if snapshots is not None:
+            snapshots[k] = [list(frames_coded[j << k]) for j in range(len(frames_coded) >> k)]
+
+    keep(stages)
+    for stage_idx in reversed(range(down_to, stages)):
+        step = 2 ** stage_idx
+        me_num = min(codec.num_me_stages - 1, stage_idx)
+        for group_idx in reversed(range(len(frames_coded) >> (stage_idx + 1))):
+            i_ref = group_idx * 2 * step
+            L_t, L_tc, mv_ref = frames_coded[i_ref]
+            H_t, H_tc, mv_hat = frames_coded[i_ref + step]
+            assert mv_ref is None
+            ref, cur = codec.inverse_MCTF(L_t, H_t, mv_hat, stage_idx=me_num)
+            ref_c, cur_c = codec.inverse_MCTF(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
+            frames_coded[i_ref] = [ref, ref_c, None]
+            frames_coded[i_ref + step] = [cur, cur_c, None]
+        keep(stage_idx)
+    return frames_coded
+
+
+def _check_decode_args(level, motion_fill, ll_order=None):
+    check_level(level)
+    if not any(motion_fill is v for v in (True, False)):
+        raise ValueError(f"motion_fill is True or False (got {motion_fill!r})")
+    if ll_order is not None and ll_order not in pmctf_gop.LL_ORDERS:
+        raise ValueError(f"ll_order must be one of {pmctf_gop.LL_ORDERS}")
+
+
+def decode_gop_files_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, level, psize=128, me_downsample=1,
+                           ll_order="plane", motion_fill=False):
+    """pmctf_gop.decode_gop_files at temporal level `level`: only the files of layer_file_names(gop, level, motion_fill)
+    are opened (anything else in the folder may be absent, cut short or garbage); a missing, truncated or surplus-length
+    file of that set raises a ValueError naming it.  The picture files go through one batch, under it the motion files of
+    the stages >= kk decode stage by stage in coding order with the context reset per stage (a reduced-resolution motion
+    stream at the size it was coded at), and decode_gop's loop runs for the stages S-1 .. kk with the GOP's own stage
+    numbers.  The pictures are the list's entries at j * 2^kk; for kk == S there is no synthesis and the picture is the
+    decoded L planes as they are.
+    motion_fill=True: full-rate output from the same picture files.  The motion of the stages < kk is decoded too, the H
+    planes of those stages are zero tensors, and the result is exactly pmctf_gop.decode_gop of those inputs: every picture
+    of the GOP.
+    Returns {"frames": [[Y, UV, None]] (padded), "times": their offsets within the GOP, "frames_coded": the decoded
+    entries the synthesis consumed ([None, None, None] where nothing was read; zero H planes under motion_fill), "stages":
+    S, "files": the names read, in order, "bytes_read": their sizes summed}."""
+    import torch
+    _check_decode_args(level, motion_fill, ll_order)
+    stages = gop_stages(gop)
+    kk = min(level, stages)
+    with torch.no_grad():
+        frames_coded, read, nbytes = _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize,
+                                                     me_downsample, ll_order, kk, motion_fill)
+        if motion_fill:
+            for stage, _, i_cur in (pmctf_gop.gop_pairs(gop) if gop != 1 else []):
+                if stage < kk:
+                    frames_coded[i_cur][0] = torch.zeros_like(frames_coded[0][0])
+                    frames_coded[i_cur][1] = torch.zeros_like(frames_coded[0][1])
+            coded = [list(fc) for fc in frames_coded]
+            rec = pmctf_gop.decode_gop(codec, frames_coded)
+            times = list(range(gop))
+        else:
+            coded = [list(fc) for fc in frames_coded]
+            _synthesis(codec, frames_coded, stages, kk)
+            times = [j << kk for j in range(gop >> kk)]
+            rec = [frames_coded[t] for t in times]
+    return {"frames": rec, "times": times, "frames_coded": coded, "stages": stages, "files": read, "bytes_read": nbytes}
+
+
+# ------------------------------------------------------------------------------------------------------------ layer hashes
+def _max_level(gops):
+    return max(gop_stages(g[1]) for g in gops)
+
+
+def _layer_path(bin_folder):
+    return os.path.join(bin_folder, LAYER_HASHES)
+
+
+def _check_layer_record(path, record, gops):
+    """the fields of a layer hash record against the folder's layout (see read_layer_hashes)"""
+    if not isinstance(record, dict) or record.get("format_version") != LAYER_HASH_FORMAT_VERSION:
+        got = record.get("format_version") if isinstance(record, dict) else None
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {LAYER_HASH_FORMAT_VERSION}")
+    want = {"format_version", "level", "layers"}
+    if set(record) != want:
+        raise ValueError(f"{path}: fields missing {sorted(want - set(record))}, unknown {sorted(set(record) - want)}")
+    level, layers = record["level"], record["layers"]
+    if level not in pmctf_gop.HASH_LEVELS:
+        raise ValueError(f"{path}: level {level!r}, this decoder knows {pmctf_gop.HASH_LEVELS}")
+    names = [str(k) for k in range(1, _max_level(gops) + 1)]
+    if not isinstance(layers, dict) or sorted(layers) != sorted(names):
+        got = sorted(layers) if isinstance(layers, dict) else layers
+        raise ValueError(f"{path}: layers {got!r}, the sequence has the layers {names}")
+    keys = set(pmctf_gop.HASH_KEYS[level]) | {"index"}
+    for k in names:
+        recs = layers[k]
+        if not isinstance(recs, list) or not all(isinstance(r, dict) and set(r) == keys for r in recs):
+            raise ValueError(f"{path}: layer {k}: a list of records that hold exactly 'index' and "
+                             f"{pmctf_gop.HASH_KEYS[level]}")
+        times = [t for _, t in layer_times(gops, int(k))]
+        if [r["index"] for r in recs] != times:
+            raise ValueError(f"{path}: layer {k}: source indices {[r['index'] for r in recs]}, the layout gives {times}")
+        for r in recs:
+            for key, v in r.items():
+                if key != "index" and (not _is_int(v) or not 0 <= v <= 0xffffffff):
+                    raise ValueError(f"{path}: layer {k}: picture {r['index']}: {key} is not a 32-bit value ({v!r})")
+
+
+def read_layer_hashes(bin_folder):
+    """-> {"format_version", "level", "layers": {"1": [{"index", *HASH_KEYS[level]}], ...}} of bin_folder/layer_hashes.json.
+    ValueError naming the path for a missing or malformed file, another version, unknown or missing fields, an unknown
+    hash level, layers other than 1..log2(largest GOP), and a layer whose source indices are not layer_times of the
+    folder's layout."""
+    path = _layer_path(bin_folder)
+    _, gops = pmctf_gop.sequence_layout(bin_folder)
+    try:
+        with open(path) as f:
+            record = json.load(f)
+    except FileNotFoundError:
+        raise ValueError(f"{path}: missing (write_layer_hashes was not run on the folder)") from None
+    except (json.JSONDecodeError, UnicodeDecodeError) as e:
+        raise ValueError(f"{path}: not a layer hash file ({e})") from None
+    _check_layer_record(path, record, gops)
+    return record
+
+
+def write_layer_hashes(codec, bin_folder, hash_level=None):
+    """Decode bin_folder fully, GOP by GOP, and write bin_folder/layer_hashes.json: for every k from 1 to log2 of the
+    largest GOP the CRC-32 (pmctf_gop.picture_hashes) of every picture of layer k, taken out of the SAME synthesis as the
+    full-rate pictures, from the list as it stands once stage min(k, S) is undone.  Where picture_hashes.json is present
+    every GOP's full-rate pictures are checked against it first (PictureHashMismatch, nothing written): the layer record
+    is then anchored to the encoder's own reconstruction.  hash_level: that of picture_hashes.json by default, or "u8"
+    ("u16" above 8 bits) without one.  -> the path written."""
+    import torch
+    G = pmctf_gop
+    header, gops = G.sequence_layout(bin_folder)
+    bitdepth = G.read_picture_format(bin_folder)
+    recorded = None
+    if os.path.exists(os.path.join(bin_folder, G.PICTURE_HASHES)):
+        recorded = G.read_picture_hashes(bin_folder, header["frame_num"])
+    if hash_level is None:
+        hash_level = recorded["level"] if recorded is not None else ("u16" if bitdepth > 8 else "u8")
+    G.check_hash_level(hash_level, bitdepth)
+    if os.path.exists(os.path.join(bin_folder, LAYER_EXTRACT)):
+        raise ValueError(f"{os.path.join(bin_folder, LAYER_EXTRACT)}: an extracted folder cannot be decoded fully")
+    G.check_sequence_header(header, G.codec_header_fields(codec))
+    h, w = header["height"], header["width"]
+    top = _max_level(gops)
+    layers = {str(k): [] for k in range(1, top + 1)}
+    with torch.no_grad():
+        for g, (first, size, psize, me_downsample) in enumerate(gops):
+            folder = os.path.join(bin_folder, G.gop_folder(g))
+            stages = gop_stages(size)
+            coded, _, _ = _read_gop_layer(codec, folder, size, h, w, header["q_index"], psize, me_downsample,
+                                          header["ll_order"], 0, False)
+            shots = {}
+            _synthesis(codec, coded, stages, 0, shots)
+            if recorded is not None:
+                bad = G.compare_hash_records(G.picture_hashes(shots[0], h, w, recorded["level"], bitdepth),
+                                             recorded["frames"][first:first + size], first, gop=g, folder=folder)
+                if bad:
+                    raise G.PictureHashMismatch(bad[0])
+            for k in range(1, top + 1):
+                kk = min(k, stages)
+                for j, rec in enumerate(G.picture_hashes(shots[kk], h, w, hash_level, bitdepth)):
+                    layers[str(k)].append(dict({key: int(rec[key]) for key in G.HASH_KEYS[hash_level]},
+                                               index=first + (j << kk)))
+    record = {"format_version": LAYER_HASH_FORMAT_VERSION, "level": hash_level, "layers": layers}
+    path = _layer_path(bin_folder)
+    _check_layer_record(path, record, gops)
+    with open(path, "w") as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return path
+
+
+# ------------------------------------------------------------------------------------------------------------- extraction
+def read_layer_extract(bin_folder):
+    """-> None for a folder without layer_extract.json, else its record {"format_version", "min_level", "motion"};
+    ValueError naming the path for a malformed file, another version or other fields"""
+    path = os.path.join(bin_folder, LAYER_EXTRACT)
+    try:
+        with open(path) as f:
+            record = json.load(f)
+    except FileNotFoundError:
+        return None
+    except (json.JSONDecodeError, UnicodeDecodeError) as e:
+        raise ValueError(f"{path}: not a layer extract file ({e})") from None
+    if not isinstance(record, dict) or record.get("format_version") != LAYER_EXTRACT_VERSION:
+        got = record.get("format_version") if isinstance(record, dict) else None
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {LAYER_EXTRACT_VERSION}")
+    if set(record) != {"format_version", "min_level", "motion"}:
+        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version, min_level and motion")
+    if not _is_int(record["min_level"]) or record["min_level"] < 0 or not isinstance(record["motion"], bool):
+        raise ValueError(f"{path}: min_level {record['min_level']!r}, motion {record['motion']!r}")
+    return record
+
+
+def _check_against_extract(bin_folder, level, motion_fill):
+    """refuse what an extracted folder cannot give: a level below its min_level, motion_fill without its motion files"""
+    marker = read_layer_extract(bin_folder)
+    if marker is None:
+        return
+    path = os.path.join(bin_folder, LAYER_EXTRACT)
+    if level < marker["min_level"]:
+        raise ValueError(f"{path}: the folder holds the files of temporal level {marker['min_level']} and above, "
+                         f"level {level} cannot be decoded from it")
+    if motion_fill and not marker["motion"] and marker["min_level"] > 0:
+        raise ValueError(f"{path}: the folder was extracted without the motion files of the left-out stages "
+                         f"(motion: false), motion_fill cannot be decoded from it")
+
+
+def extract_layer(src_folder, dst_folder, level, motion_fill=False):
+    """Copy what a level-`level` decode of the sequence in src_folder reads into dst_folder (created when missing; refused
+    when not empty): the header, picture_format.json and layer_hashes.json where present, per GOP exactly
+    layer_file_names(size, level, motion_fill), and layer_extract.json {"format_version", "min_level": level, "motion":
+    motion_fill}, which decode_sequence_layer reads.  picture_hashes.json is not copied: the folder cannot produce those
+    pictures.  No codec, no GPU.  -> the relative paths written, sorted."""
+    import shutil
+    _check_decode_args(level, motion_fill)
+    G = pmctf_gop
+    _, gops = G.sequence_layout(src_folder)
+    _check_against_extract(src_folder, level, motion_fill)
+    if os.path.exists(dst_folder) and (not os.path.isdir(dst_folder) or os.listdir(dst_folder)):
+        raise ValueError(f"{dst_folder}: not an empty folder; extract_layer writes into a new or empty one")
+    copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, LAYER_HASHES)
+              if os.path.exists(os.path.join(src_folder, n))]
+    for k, g in enumerate(gops):
+        copies += [os.path.join(G.gop_folder(k), n) for n in layer_file_names(g[1], level, motion_fill)]
+    for rel in copies:
+        if not os.path.isfile(os.path.join(src_folder, rel)):
+            raise ValueError(f"{os.path.join(src_folder, rel)}: missing")
+    os.makedirs(dst_folder, exist_ok=True)
+    for rel in copies:
+        os.makedirs(os.path.dirname(os.path.join(dst_folder, rel)), exist_ok=True)
+        shutil.copyfile(os.path.join(src_folder, rel), os.path.join(dst_folder, rel))
+    with open(os.path.join(dst_folder, LAYER_EXTRACT), "w") as f:
+        json.dump({"format_version": LAYER_EXTRACT_VERSION, "min_level": level, "motion": bool(motion_fill)}, f, indent=1,
+                  sort_keys=True)
+        f.write("\n")
+    return sorted(copies + [LAYER_EXTRACT])
+
+
+# ------------------------------------------------------------------------------------------------------------ a sequence
+def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False):
+    """pmctf_gop.decode_sequence_checked at temporal level `level`: the folder's header (either kind), its
+    picture_format.json (16-bit output above 8 bits, png_out refused) and the codec checks are the same, and every GOP is
+    decoded with decode_gop_files_layer from its own size, psize and me_downsample.  The .yuv holds the pictures of
+    layer_times in order; the PNGs are named by SOURCE picture index.
+    level=0 without motion_fill writes the bytes decode_sequence writes and verifies against picture_hashes.json as it
+    does.  Above level 0 the pictures are verified against layer_hashes.json (write_layer_hashes) under the same four
+    verify modes: "auto" checks when the file is there, True insists on it, False never looks, "report" checks, writes
+    everything and lists the mismatches; under "auto" and True the first mismatch raises PictureHashMismatch with none of
+    that GOP's pictures written.  motion_fill output is never verified, and verify=True is refused with it.
+    A folder written by extract_layer (layer_extract.json) refuses a level below its min_level, and motion_fill when it
+    holds no motion files for the left-out stages.
+    Returns decode_sequence's dict ("frames", "seconds", "verified", "hash_mismatches", "header", "bitdepth") plus "level",
+    "times": the source index of every written picture, and "bytes_read": the sizes of the files read, layer_bytes."""
+    import contextlib
+    import time
+    import torch
+    G = pmctf_gop
+    _check_decode_args(level, motion_fill)
+    if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
+        raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
+    if motion_fill and verify is True:
+        raise ValueError("motion_fill output is never verified: there is no record of it (verify=True refused)")
+    if yuv_out is None and png_out is None:
+        raise ValueError("nothing to write: give yuv_out, png_out or both")
+    header, gops = G.sequence_layout(bin_folder)
+    _check_against_extract(bin_folder, level, motion_fill)
+    bitdepth = G.read_picture_format(bin_folder)
+    if bitdepth > 8 and png_out is not None:
+        raise ValueError(f"{os.path.join(bin_folder, G.PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
+                         f"8-bit PNGs; decode to a .yuv")
+    G.check_sequence_header(header, G.codec_header_fields(codec))
+    dev = codec.engine().dev
+    if device is not None and torch.device(device).type != dev.type:
+        raise ValueError(f"the codec lives on {dev}, not on {device}")
+    # the record the pictures are checked against: picture_hashes.json at level 0, layer_hashes.json above
+    recorded, hash_level = None, None
+    top = _max_level(gops)
+    if motion_fill or verify is False:
+        pass
+    elif level == 0 or top == 0:                   # a sequence of lone pictures has one layer, the full-rate one
+        if verify != "auto" or os.path.exists(os.path.join(bin_folder, G.PICTURE_HASHES)):
+            full = G.read_picture_hashes(bin_folder, header["frame_num"])
+            recorded, hash_level = full["frames"], full["level"]
+    elif verify != "auto" or os.path.exists(_layer_path(bin_folder)):
+        layers = read_layer_hashes(bin_folder)
+        recorded, hash_level = layers["layers"][str(min(level, top))], layers["level"]
+    h, w = header["height"], header["width"]
+    shapes, seconds, mismatches, times = [], [], [], []
+    verified = at = nbytes = 0
+    with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
+        for k, (first, size, psize, me_downsample) in enumerate(gops):
+            t0 = time.time()
+            folder = os.path.join(bin_folder, G.gop_folder(k))
+            out = decode_gop_files_layer(codec, folder, size, h, w, header["q_index"], level, psize=psize,
+                                         me_downsample=me_downsample, ll_order=header["ll_order"], motion_fill=motion_fill)
+            source = [first + t for t in out["times"]]
+            if recorded is not None:
+                got = G.picture_hashes(out["frames"], h, w, hash_level, bitdepth)
+                want = recorded[first:first + size] if level == 0 or top == 0 else recorded[at:at + len(source)]
+                bad = []
+                for t, a, b in zip(source, got, want):
+                    bad += G.compare_hash_records([a], [b], t, gop=k, folder=folder)
+                if bad and verify != "report":
+                    raise G.PictureHashMismatch(bad[0])
+                mismatches += bad
+                verified += len(source)
+            if f is not None:
+                pictures = G.frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
+                    G.frames_to_u8(out["frames"], h, w)
+                for planes in pictures:
+                    for p in planes:
+                        f.write(p.tobytes(order="C"))
+            if png_out is not None:
+                for t, rgb in zip(source, G.frames_to_rgb8(out["frames"], h, w)):
+                    G.write_pngs(png_out, t, [rgb])
+            at += len(source)
+            nbytes += out["bytes_read"]
+            times += source
+            shapes += [(h, w)] * len(source)
+            seconds.append(time.time() - t0)
+    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
+            "bitdepth": bitdepth, "level": level, "times": times, "bytes_read": nbytes}

@@ -12,7 +12,12 @@ with.  The decoder refuses a header whose arithmetic profile (PMCTF_PRECISION) o
 every decoded picture is checked against them (a mismatch stops the decoder before that GOP is written) unless --no-verify
 is given; --verify insists on the hashes being there, --verify-report writes everything and lists the mismatches.
 A folder coded with --bitdepth above 8 (it holds picture_format.json) is written as little-endian 16-bit samples of that
-depth; the depth found is printed with the summary."""
+depth; the depth found is printed with the summary.
+--temporal-level K (pmctf_layers.decode_sequence_layer) decodes the sequence at 1/2^K of its frame rate from the files of
+that level alone: one picture per 2^K of a GOP, a shallower GOP its one low-band picture; the PNGs keep the source
+indices.  Level 1 and above are checked against layer_hashes.json (tools/encode_sequence.py --layer-hashes).
+--motion-fill gives every picture from the same picture files: the motion of the left-out stages is read too and their
+high-band pictures are taken as zero; that output has no hashes to be checked against."""
 import argparse
 import json
 import os
@@ -35,9 +40,18 @@ def main():
     v.add_argument("--no-verify", dest="verify", action="store_const", const=False, help="do not check picture hashes")
     v.add_argument("--verify-report", dest="verify", action="store_const", const="report",
                    help="check, write every picture all the same, list the mismatches and exit with status 1 if there are any")
+    ap.add_argument("--temporal-level", type=int, metavar="K",
+                    help="decode at 1/2^K of the frame rate from the files of that level alone (default: everything)")
+    ap.add_argument("--motion-fill", action="store_true",
+                    help="with --temporal-level: full frame rate, the left-out high bands taken as zero (never verified)")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args()
+    layered = a.temporal_level is not None or a.motion_fill
+    if layered and (a.temporal_level or 0) < 0:
+        ap.error("--temporal-level is 0 or more")
+    if a.motion_fill and a.verify is True:
+        ap.error("--motion-fill output has no hashes: it cannot be combined with --verify")
     if a.yuv_out is None and a.png is None:
         ap.error("give OUT.yuv, --png DIR or both")
     import torch
@@ -55,14 +69,22 @@ def main():
     net.update(force=True)
     with torch.no_grad():
         try:
-            out = pmctf_gop.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png, verify=a.verify)
+            if layered:
+                import pmctf_layers
+                out = pmctf_layers.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
+                                                         png_out=a.png, verify=a.verify, motion_fill=a.motion_fill)
+            else:
+                out = pmctf_gop.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
+                                                        verify=a.verify)
         except pmctf_gop.PictureHashMismatch as e:
             sys.exit(f"picture hash mismatch: {e}")
     n = len(out["frames"])
     print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out, "png": a.png,
                       "bitdepth": out["bitdepth"],
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
-                      "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"])}))
+                      "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"]),
+                      **({"temporal_level": out["level"], "motion_fill": a.motion_fill, "bytes_read": out["bytes_read"]}
+                         if layered else {})}))
     for m in out["hash_mismatches"]:
         print(pmctf_gop.describe_hash_mismatch(m), file=sys.stderr)
     if out["hash_mismatches"]:

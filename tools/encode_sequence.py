@@ -16,7 +16,10 @@ becomes a list of GOPs of 1, 2, 4, ... up to --gop pictures, so every picture of
 all of them).  fill takes the largest GOP that still fits; scenecut first looks for scene changes (luma histogram and mean
 absolute difference on the GPU, thresholds --hd-min and --mad-min) and starts a GOP at each; search runs the reference's
 rate-distortion search per window of --gop pictures.  The chosen list and the cuts go to stderr; BIN_FOLDER then holds
-gop_structure.json instead of sequence.json, which tools/decode_sequence.py reads as well."""
+gop_structure.json instead of sequence.json, which tools/decode_sequence.py reads as well.
+--layer-hashes: after the encode the folder is decoded once more (pmctf_layers.write_layer_hashes, checked against the
+picture hashes where there are any) and BIN_FOLDER/layer_hashes.json records the CRC-32 of every picture of every temporal
+layer, which tools/decode_sequence.py --temporal-level K checks."""
 import argparse
 import os
 import sys
@@ -48,6 +51,8 @@ def main():
                     help="record picture hashes: of the written planes (u8; u16 with --bitdepth above 8), and of the padded "
                          "float32 reconstructions (f32)")
     ap.add_argument("--bitdepth", type=int, default=8, help="bit depth of a .yuv source: 8, or 9..16 for 16-bit samples")
+    ap.add_argument("--layer-hashes", action="store_true",
+                    help="also record the hashes of the temporal layers (layer_hashes.json), from a full decode of the folder")
     ap.add_argument("source", help=".yuv file or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args()
@@ -107,6 +112,13 @@ def main():
             print("GOPs (first picture: size, motion down-sampling): " +
                   ", ".join(f"{g['first']}: {g['size']}" + (f" /{g['me_downsample']}" if g["me_downsample"] != 1 else "")
                             for g in out["gops"]), file=sys.stderr)
+        if a.layer_hashes:
+            import pmctf_layers
+            try:
+                path = pmctf_layers.write_layer_hashes(net, a.bin_folder)
+            except pmctf_gop.PictureHashMismatch as e:
+                sys.exit(f"picture hash mismatch, no layer hashes written: {e}")
+            print(f"layer hashes: {path}", file=sys.stderr)
     print(out["json"])
 
 
