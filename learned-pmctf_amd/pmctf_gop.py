@@ -605,6 +605,7 @@ LL_ORDERS = ("position", "plane")
 
 
 GOP_STRUCTURE = "gop_structure.json"                  # the header of a structured folder (pmctf_seq), instead of sequence.json
+GOP_STRUCTURE_VERSION_Q = 2                           # its format version whose GOP entries carry their own q_index
 
 
 def sequence_layout(bin_folder):
@@ -618,6 +619,14 @@ def sequence_layout(bin_folder):
     header = read_sequence_header(bin_folder)
     gop = header["gop"]
     return header, [(k * gop, gop, header["psize"], header["me_downsample"]) for k in range(header["frame_num"] // gop)]
+
+
+def gop_q_indexes(header, n_gops):
+    """-> the q_index of each of the n_gops GOPs of a folder: a gop_structure.json of format version 2
+    (pmctf_rate.encode_sequence_rate) holds one per GOP; every other header has one for the sequence"""
+    if GOP_STRUCTURE_VERSION_Q == header.get("format_version") and "gops" in header:
+        return [g["q_index"] for g in header["gops"]]
+    return [header["q_index"]] * n_gops
 
 
 def gop_folder(k):
@@ -1103,12 +1112,13 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
         recorded = read_picture_hashes(bin_folder, header["frame_num"])
     h, w = header["height"], header["width"]
+    q_indexes = gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, verified = [], [], [], 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
         for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, gop_folder(k))
-            out = decode_gop_files(codec, folder, size, h, w, header["q_index"], psize=psize, me_downsample=me_downsample,
+            out = decode_gop_files(codec, folder, size, h, w, q_indexes[k], psize=psize, me_downsample=me_downsample,
                                    ll_order=header["ll_order"])
             if recorded is not None:
                 bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"], bitdepth),

@@ -308,12 +308,13 @@ def write_layer_hashes(codec, bin_folder, hash_level=None):
     G.check_sequence_header(header, G.codec_header_fields(codec))
     h, w = header["height"], header["width"]
     top = _max_level(gops)
+    q_indexes = G.gop_q_indexes(header, len(gops))
     layers = {str(k): [] for k in range(1, top + 1)}
     with torch.no_grad():
         for g, (first, size, psize, me_downsample) in enumerate(gops):
             folder = os.path.join(bin_folder, G.gop_folder(g))
             stages = gop_stages(size)
-            coded, _, _ = _read_gop_layer(codec, folder, size, h, w, header["q_index"], psize, me_downsample,
+            coded, _, _ = _read_gop_layer(codec, folder, size, h, w, q_indexes[g], psize, me_downsample,
                                           header["ll_order"], 0, False)
             shots = {}
             _synthesis(codec, coded, stages, 0, shots)
@@ -452,13 +453,14 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
         layers = read_layer_hashes(bin_folder)
         recorded, hash_level = layers["layers"][str(min(level, top))], layers["level"]
     h, w = header["height"], header["width"]
+    q_indexes = G.gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, times = [], [], [], []
     verified = at = nbytes = 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
         for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, G.gop_folder(k))
-            out = decode_gop_files_layer(codec, folder, size, h, w, header["q_index"], level, psize=psize,
+            out = decode_gop_files_layer(codec, folder, size, h, w, q_indexes[k], level, psize=psize,
                                          me_downsample=me_downsample, ll_order=header["ll_order"], motion_fill=motion_fill)
             source = [first + t for t in out["times"]]
             if recorded is not None:

@@ -17,12 +17,14 @@ import json
 import os
 
 import pmctf_gop
-from pmctf_gop import GOP_STRUCTURE
+from pmctf_gop import GOP_STRUCTURE, GOP_STRUCTURE_VERSION_Q      # 2: every GOP entry carries its own q_index (pmctf_rate)
 
-GOP_STRUCTURE_VERSION = 1
+GOP_STRUCTURE_VERSION = 1                             # one q_index for the sequence
 STRUCTURE_FIELDS = ("width", "height", "frame_num", "max_gop", "q_index", "num_me_stages", "ll_order", "precision",
                     "aten_threads", "gops")
 GOP_FIELDS = ("first", "size", "me_downsample", "psize")
+GOP_FIELDS_Q = GOP_FIELDS + ("q_index",)              # the entries of format version 2
+Q_NUM = 21                                            # pWave.get_qp_num(): q_index is one of 0..20
 STRUCTURES = ("fill", "scenecut", "search")
 DS_FACTORS = (1, 2, 4, 8)
 ACTIVITY_BATCH = 16                                   # pictures per device->host copy of sequence_activity
@@ -130,17 +132,25 @@ def sequence_activity(reader_factory, frame_num, device, bitdepth=8):
 
 
 # ------------------------------------------------------------------------------------------------------------- the header
-def _check_gops(where, gops, frame_num, max_gop):
+def _check_gops(where, gops, frame_num, max_gop, version=GOP_STRUCTURE_VERSION):
     """the list of a structure header: contiguous from 0 to frame_num, sizes powers of two <= max_gop, me_downsample in
-    DS_FACTORS, psize ca_psize(me_downsample) or the one other value the sequence uses"""
+    DS_FACTORS, psize ca_psize(me_downsample) or the one other value the sequence uses.  version 2: every entry also holds
+    its q_index, one of 0..20; entries of the other version are refused with a message that names the format version."""
     if not isinstance(gops, list) or not gops:
         raise ValueError(f"{where}: gops is a non-empty list")
+    fields, other = (GOP_FIELDS_Q, GOP_FIELDS) if version == GOP_STRUCTURE_VERSION_Q else (GOP_FIELDS, GOP_FIELDS_Q)
     first, own = 0, set()
     for k, g in enumerate(gops):
-        if not isinstance(g, dict) or set(g) != set(GOP_FIELDS):
-            raise ValueError(f"{where}: gops[{k}] holds exactly {GOP_FIELDS}")
-        if not all(_is_int(g[f]) for f in GOP_FIELDS):
+        if isinstance(g, dict) and set(g) == set(other):
+            raise ValueError(f"{where}: format version {version}: gops[{k}] " +
+                             ("has no q_index, which every entry of version 2 holds" if version == GOP_STRUCTURE_VERSION_Q
+                              else "carries q_index, which belongs to version 2"))
+        if not isinstance(g, dict) or set(g) != set(fields):
+            raise ValueError(f"{where}: gops[{k}] holds exactly {fields}")
+        if not all(_is_int(g[f]) for f in fields):
             raise ValueError(f"{where}: gops[{k}]: every field is an integer ({g!r})")
+        if version == GOP_STRUCTURE_VERSION_Q and not 0 <= g["q_index"] < Q_NUM:
+            raise ValueError(f"{where}: gops[{k}]: q_index {g['q_index']} is not one of 0..{Q_NUM - 1}")
         if not _power_of_two(g["size"]) or g["size"] > max_gop:
             raise ValueError(f"{where}: gops[{k}]: size {g['size']} is not a power of two up to max_gop {max_gop}")
         if g["first"] != first:
@@ -160,6 +170,7 @@ def _check_gops(where, gops, frame_num, max_gop):
 
 
 def _check_structure(where, record):
+    version = record["format_version"]
     for k in ("width", "height", "frame_num", "max_gop", "q_index", "num_me_stages", "aten_threads"):
         if not _is_int(record[k]):
             raise ValueError(f"{where}: {k} is an integer (got {record[k]!r})")
@@ -171,17 +182,26 @@ def _check_structure(where, record):
         raise ValueError(f"{where}: ll_order {record['ll_order']!r}")
     if not isinstance(record["precision"], str):
         raise ValueError(f"{where}: precision {record['precision']!r}")
-    _check_gops(where, record["gops"], record["frame_num"], record["max_gop"])
+    _check_gops(where, record["gops"], record["frame_num"], record["max_gop"], version)
+    if version == GOP_STRUCTURE_VERSION_Q and record["q_index"] != record["gops"][0]["q_index"]:
+        raise ValueError(f"{where}: format version {version}: q_index {record['q_index']} is not the first GOP's "
+                         f"({record['gops'][0]['q_index']})")
 
 
 def write_gop_structure(bin_folder, **fields):
     """bin_folder/gop_structure.json: format version + STRUCTURE_FIELDS (all required, nothing else accepted); gops is the
-    list [{"first", "size", "me_downsample", "psize"}] in order.  Checked as read_gop_structure checks it."""
+    list [{"first", "size", "me_downsample", "psize"}] in order.  Checked as read_gop_structure checks it.
+    Entries that all carry "q_index" as well (0..20, the first one's equal to the sequence's q_index) give format version 2,
+    entries without it version 1, as ever; a list with both kinds is refused."""
     path = os.path.join(bin_folder, GOP_STRUCTURE)
     if set(fields) != set(STRUCTURE_FIELDS):
         raise ValueError(f"{path}: fields missing {sorted(set(STRUCTURE_FIELDS) - set(fields))}, "
                          f"unknown {sorted(set(fields) - set(STRUCTURE_FIELDS))}")
-    record = {"format_version": GOP_STRUCTURE_VERSION}
+    with_q = {"q_index" in g for g in fields["gops"] if isinstance(g, dict)} if isinstance(fields["gops"], list) else set()
+    if len(with_q) > 1:
+        raise ValueError(f"{path}: gops: some entries carry q_index and some do not; format version 1 has none, "
+                         f"version 2 one in every entry")
+    record = {"format_version": GOP_STRUCTURE_VERSION_Q if with_q == {True} else GOP_STRUCTURE_VERSION}
     record.update({k: fields[k] for k in STRUCTURE_FIELDS})
     record["gops"] = [dict(g) if isinstance(g, dict) else g for g in fields["gops"]] if isinstance(fields["gops"], list) \
         else fields["gops"]
@@ -193,9 +213,11 @@ def write_gop_structure(bin_folder, **fields):
 
 
 def read_gop_structure(bin_folder):
-    """-> the record of bin_folder/gop_structure.json.  ValueError naming the path for a missing or malformed file, another
-    version, unknown or missing fields, sizes that are not powers of two <= max_gop, `first` values that are not the
-    running sum, a list that does not end at frame_num, a me_downsample outside {1, 2, 4, 8}, a psize other than
+    """-> the record of bin_folder/gop_structure.json, format version 1 or 2 (2: a q_index in every GOP entry, see
+    write_gop_structure).  ValueError naming the path for a missing or malformed file, another version, entries of the
+    other version (the message names the format version), unknown or missing fields, a version-2 q_index outside 0..20 or
+    other than the first GOP's, sizes that are not powers of two <= max_gop, `first` values that are not the running sum,
+    a list that does not end at frame_num, a me_downsample outside {1, 2, 4, 8}, a psize other than
     ca_psize(me_downsample) or the sequence's own, and for a folder that also holds a sequence.json."""
     path = os.path.join(bin_folder, GOP_STRUCTURE)
     try:
@@ -207,9 +229,11 @@ def read_gop_structure(bin_folder):
         raise ValueError(f"{path}: not a GOP structure file ({e})") from None
     if os.path.exists(os.path.join(bin_folder, pmctf_gop.SEQUENCE_HEADER)):
         raise ValueError(f"{path}: the folder also holds {pmctf_gop.SEQUENCE_HEADER}; a sequence has one header")
-    if not isinstance(record, dict) or record.get("format_version") != GOP_STRUCTURE_VERSION:
+    versions = (GOP_STRUCTURE_VERSION, GOP_STRUCTURE_VERSION_Q)
+    if not isinstance(record, dict) or not _is_int(record.get("format_version")) or record["format_version"] not in versions:
         got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {GOP_STRUCTURE_VERSION}")
+        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {GOP_STRUCTURE_VERSION} and version "
+                         f"{GOP_STRUCTURE_VERSION_Q}")
     want = set(STRUCTURE_FIELDS) | {"format_version"}
     if set(record) != want:
         raise ValueError(f"{path}: fields missing {sorted(want - set(record))}, unknown {sorted(set(record) - want)}")
@@ -255,6 +279,20 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     Returns encode_sequence's dictionary (frame_types: 0 for the first picture of every GOP, else 1; the two "average ms"
     lines only when a pair was coded) plus "gops": [{"first", "size", "me_downsample", "psize"}], and "cuts" and "activity"
     (scenecut), "searches": [{"first", "gop_choice", "ds_choice", "tested_opts", "trials"}] (search)."""
+    return _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, None, bin_folder, device, structure,
+                            hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
+                            picture_hash, bitdepth, msssim)
+
+
+def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, choose, bin_folder, device, structure,
+                     hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
+                     picture_hash, bitdepth, msssim, what="encode_sequence_gops"):
+    """The body of encode_sequence_gops, shared with pmctf_rate.encode_sequence_rate.  choose is None: every GOP is coded
+    once, at q_index, into its folder.  Otherwise q_index is None and choose(k, g, trial) decides GOP k's: trial(q, folder)
+    codes the GOP (g: its entry of the list) at q into folder (created) and returns {"q_index", "folder", "bits": 8 x the
+    sizes of its files, "seconds", ...}; choose returns the trial it accepts, whose files it has moved to
+    bin_folder/gop_{k:05d}.  Only the accepted trial is reconstructed, reported and counted in the "average ms" lines; the
+    GOP entries then carry "q_index" and the header is format version 2."""
     import io
     import time
     import torch
@@ -295,7 +333,7 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     from pMCTF.utils.yuv_reader import YUVReader
     on_device = src_format == "png" or ingest == "device"
     if on_device or structure == "scenecut":
-        G._need_gpu(device, f"encode_sequence_gops(src_format={src_format!r}, ingest={ingest!r}, structure={structure!r})")
+        G._need_gpu(device, f"{what}(src_format={src_format!r}, ingest={ingest!r}, structure={structure!r})")
 
     def make_reader():
         if src_format == "png":
@@ -326,18 +364,32 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     pairs = 0
     seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
 
-    def code(g, padded, orig, h, w):
-        """one GOP of the list: its folder, its files, its reconstruction, its rows of the tables"""
-        nonlocal pairs
-        folder = os.path.join(bin_folder, G.gop_folder(len(gops)))
+    def trial(g, padded, h, w, q, folder):
+        """one GOP coded once, at q, into folder: its files and what report needs of it"""
         os.makedirs(folder, exist_ok=True)
+        t = {"q_index": q, "folder": folder}
+        t0 = time.time()
         if g["size"] == 1:
-            r = codec.encode_lone_picture(padded[0], folder, w, h, psize=g["psize"], skip_decoding=skip_decoding,
-                                          q_index=q_index)
+            t["lone"] = codec.encode_lone_picture(padded[0], folder, w, h, psize=g["psize"], skip_decoding=skip_decoding,
+                                                  q_index=q)
+            names = ("0_main.bin", "0_C_main.bin")
+        else:
+            t["enc"] = G.encode_gop(codec, padded, h, w, q, folder, skip_decoding=skip_decoding, psize=g["psize"],
+                                    me_downsample=g["me_downsample"])
+            names = G.gop_file_names(g["size"])
+        if choose is not None:
+            t["seconds"] = time.time() - t0
+            t["bits"] = 8 * sum(os.path.getsize(os.path.join(folder, n)) for n in names)
+        return t
+
+    def report(g, t, orig, h, w):
+        """the accepted coding of a GOP: its reconstruction, its rows of the tables"""
+        nonlocal pairs
+        if g["size"] == 1:
+            r = t["lone"]
             rec, bits, bits_mv = [[r["L_t"], r["L_tc"], None]], [float(r["bit_L"])], [0.0]
         else:
-            enc = G.encode_gop(codec, padded, h, w, q_index, folder, skip_decoding=skip_decoding, psize=g["psize"],
-                               me_downsample=g["me_downsample"])
+            enc = t["enc"]
             for r in enc["results"]:
                 pairs += 1
                 for key in seconds:
@@ -346,7 +398,16 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
             rec, bits, bits_mv = G.decode_gop(codec, enc["frames_coded"]), enc["bits"], enc["bits_mv"]
         G.report_gop(rec, orig, h, w, bits, bits_mv, g["first"], tables, ssims, hashes, picture_hash=picture_hash,
                      bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
-        gops.append(dict(g))
+        gops.append(dict(g) if choose is None else dict(g, q_index=t["q_index"]))
+
+    def code(g, padded, orig, h, w):
+        """one GOP of the list: its folder, its files, its reconstruction, its rows of the tables"""
+        k = len(gops)
+        if choose is None:
+            t = trial(g, padded, h, w, q_index, os.path.join(bin_folder, G.gop_folder(k)))
+        else:
+            t = choose(k, dict(g), lambda q, folder: trial(g, padded, h, w, q, folder))
+        report(g, t, orig, h, w)
 
     try:
         with torch.no_grad():
@@ -376,7 +437,8 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
                         code(unit(first + f, s), padded, orig, h, w)
     finally:
         reader.close()
-    write_gop_structure(bin_folder, width=width, height=height, frame_num=frame_num, max_gop=max_gop, q_index=q_index,
+    write_gop_structure(bin_folder, width=width, height=height, frame_num=frame_num, max_gop=max_gop,
+                        q_index=q_index if choose is None else gops[0]["q_index"],
                         ll_order="plane" if skip_decoding else "position", gops=gops, **G.codec_header_fields(codec))
     if picture_hash is not None:
         G.write_picture_hashes(bin_folder, picture_hash, hashes)

@@ -1,0 +1,595 @@
+"""Rate control, the parts that need no GPU: the controller of pmctf_rate against tests/rate_restatement.py on seeded size
+tables, the version-2 gop_structure.json header (round trip, gop_q_indexes, every new refusal, version 1 untouched),
+verify_rate_record on dummy files under a real header, and the refusals of encode_sequence_rate and of the tool's
+arguments before anything is loaded.  Everything is exact integers."""
+import ast
+import importlib.util
+import inspect
+import json
+import os
+import random
+
+import pytest
+
+import pmctf_gop
+import pmctf_rate
+import pmctf_seq
+import rate_restatement as rr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SLACKS = (0.0, 0.05, 0.5)
+FPS = (1, 24, 30, 60, (30000, 1001), (24000, 1001), (25, 2), (7, 3))
+
+
+def test_the_module_imports_no_torch_at_module_level():
+    tree = ast.parse(open(os.path.join(ROOT, "learned-pmctf_amd", "pmctf_rate.py")).read())
+    top = set()
+    for node in tree.body:
+        if isinstance(node, ast.Import):
+            top |= {a.name.split(".")[0] for a in node.names}
+        elif isinstance(node, ast.ImportFrom):
+            top.add((node.module or "").split(".")[0])
+    assert top == {"json", "os"}, top
+
+
+# ------------------------------------------------------------------------------------------------------- the size tables
+def _table(rng, n, kind):
+    """n sizes, in bits, for the n choices"""
+    if kind == "monotone":
+        v = sorted(rng.sample(range(1, 100000), n))
+    elif kind == "ties":
+        v = sorted(rng.choice((800, 1600, 2400, 3200)) for _ in range(n))
+    else:
+        v = [rng.randrange(1, 100000) for _ in range(n)]
+    return v
+
+
+def _budgets(rng, sizes):
+    """below, between and above the sizes, on them, 0 and negative"""
+    lo, hi = min(sizes), max(sizes)
+    return [-5, 0, lo - 1, lo, rng.randint(lo, hi), sorted(sizes)[len(sizes) // 2], hi, hi + 1, 3 * hi]
+
+
+class Counted:
+    """a size function that records its calls"""
+
+    def __init__(self, fn):
+        self.fn, self.calls = fn, []
+
+    def __call__(self, *key):
+        self.calls.append(key)
+        return self.fn(*key)
+
+
+def _check_choice(got, calls, choices, start, budget, max_trials, sizes):
+    trials = got["trials"]
+    assert [c[0] for c in calls] == [q for q, _ in trials], "the trials are the calls, in order"
+    assert len(set(calls)) == len(calls) <= max_trials, "at most once per q, at most max_trials times"
+    assert all(b == sizes[choices.index(q)] for q, b in trials)
+    assert (got["q_index"], got["bits"]) in trials[-2:], "the accepted trial is the last or the one before it"
+    assert got["q_index"] == choices[got["index"]] and got["fits"] == (got["bits"] <= budget)
+    assert trials[0][0] == choices[start]
+    if not got["fits"]:
+        assert all(b > budget for _, b in trials), "nothing tried fits"
+        assert got["index"] == 0 or len(trials) == max_trials, "descends to the lowest choice, or runs out of trials"
+
+
+def test_choose_q_equals_the_restatement_everywhere():
+    rng = random.Random(20)
+    cases = 0
+    for n in range(1, 22):
+        choices = tuple(sorted(rng.sample(range(21), n)))
+        for kind in ("monotone", "other", "ties"):
+            sizes = _table(rng, n, kind)
+            for start in range(n):
+                for max_trials in range(1, 7):
+                    for slack in SLACKS:
+                        for budget in _budgets(rng, sizes):
+                            fn = Counted(lambda q: sizes[choices.index(q)])
+                            got = pmctf_rate.choose_q(fn, choices, start, budget, max_trials=max_trials, slack=slack)
+                            index, fits, bits, tried = rr.choose(lambda q: sizes[choices.index(q)], choices, start, budget,
+                                                                 max_trials, slack)
+                            assert got == {"q_index": choices[index], "index": index, "fits": fits, "bits": bits,
+                                           "trials": tried}, (choices, sizes, start, budget, max_trials, slack)
+                            _check_choice(got, fn.calls, choices, start, budget, max_trials, sizes)
+                            cases += 1
+    assert cases > 50000
+
+
+def test_choose_q_worked_examples():
+    sizes = {0: 100, 7: 200, 14: 300, 20: 400}
+    c = lambda start, budget, **kw: pmctf_rate.choose_q(sizes.__getitem__, (0, 7, 14, 20), start, budget, **kw)
+    assert c(1, 350) == {"q_index": 14, "index": 2, "fits": True, "bits": 300, "trials": [(7, 200), (14, 300), (20, 400)]}
+    assert c(1, 350, max_trials=2)["trials"] == [(7, 200), (14, 300)]                  # trials run out on the way up
+    assert c(1, 350, slack=0.4)["trials"] == [(7, 200), (14, 300)]                     # 300 is not below 0.6 x 350: stop
+    assert c(1, 350, slack=0.5)["trials"] == [(7, 200)]                                # nor 200 below 0.5 x 350
+    assert c(0, 400, slack=0.5)["trials"] == [(0, 100), (7, 200)]                      # 200 is not below 200
+    assert c(3, 250) == {"q_index": 7, "index": 1, "fits": True, "bits": 200, "trials": [(20, 400), (14, 300), (7, 200)]}
+    assert c(3, 50) == {"q_index": 0, "index": 0, "fits": False, "bits": 100,
+                        "trials": [(20, 400), (14, 300), (7, 200), (0, 100)]}
+    assert c(3, 50, max_trials=2) == {"q_index": 14, "index": 2, "fits": False, "bits": 300, "trials": [(20, 400), (14, 300)]}
+    assert c(3, 400)["trials"] == [(20, 400)] and c(0, 99)["trials"] == [(0, 100)]
+    # no assumption that the size grows with q: a dip further up is never seen, a dip further down is taken
+    odd = {0: 500, 7: 100, 14: 600, 20: 50}
+    d = lambda start, budget: pmctf_rate.choose_q(odd.__getitem__, (0, 7, 14, 20), start, budget)
+    assert d(1, 300) == {"q_index": 7, "index": 1, "fits": True, "bits": 100, "trials": [(7, 100), (14, 600)]}
+    assert d(2, 300) == {"q_index": 7, "index": 1, "fits": True, "bits": 100, "trials": [(14, 600), (7, 100)]}
+
+
+def test_gop_allocations():
+    gops = [{"first": 0, "size": 4}, {"first": 4, "size": 2, "psize": 128}, {"first": 6, "size": 1}]
+    assert pmctf_rate.gop_allocations(gops, 1000000, 30) == [133333, 66666, 33333]
+    assert pmctf_rate.gop_allocations(gops, 1000000, (30, 1)) == [133333, 66666, 33333]
+    assert pmctf_rate.gop_allocations(gops, 1000000, (30000, 1001)) == [133466, 66733, 33366]
+    assert pmctf_rate.gop_allocations(gops, 1, 30) == [0, 0, 0]
+    rng = random.Random(3)
+    for _ in range(2000):
+        sizes = [1 << rng.randrange(6) for _ in range(rng.randint(1, 6))]
+        bitrate, fps = rng.randint(1, 10 ** rng.randint(1, 12)), rng.choice(FPS)
+        assert pmctf_rate.gop_allocations([{"size": s} for s in sizes], bitrate, fps) == rr.allocations(sizes, bitrate, fps)
+
+
+def test_run_controller_equals_the_restatement_and_keeps_its_invariant():
+    rng = random.Random(21)
+    all_fit = some_miss = carried = 0
+    for case in range(3000):
+        n = rng.randint(1, 21)
+        choices = tuple(sorted(rng.sample(range(21), n)))
+        sizes = [1 << rng.randrange(5) for _ in range(rng.randint(1, 9))]
+        kind = ("monotone", "other", "ties")[case % 3]
+        scale = rng.choice((1, 1, 3))
+        table = [[scale * s * v for v in _table(rng, n, kind)] for s in sizes]
+        fps = rng.choice(FPS)
+        # a bitrate around what the tables need: from starved to generous
+        per_picture = sum(sum(t) for t in table) // (n * sum(sizes))
+        bitrate = max(1, int(per_picture * rr.fps_fraction(fps) * rng.choice((0.01, 0.3, 0.7, 1.0, 1.5, 4.0))))
+        kw = dict(q_choices=choices, q_start=rng.choice((None,) + choices), bucket_ms=rng.choice((0, 1, 40, 1000, 10 ** 6)),
+                  max_trials=rng.randint(1, 6), slack=rng.choice(SLACKS))
+        size_of = Counted(lambda k, q: table[k][choices.index(q)])
+        got = pmctf_rate.run_controller(sizes, size_of, bitrate, fps, **kw)
+        want = rr.run(sizes, lambda k, q: table[k][choices.index(q)], bitrate, fps, kw["q_choices"], kw["q_start"],
+                      kw["bucket_ms"], kw["max_trials"], kw["slack"])
+        assert got == want, (case, choices, sizes, bitrate, fps, kw)
+        assert all(set(r) == set(pmctf_rate.RECORD_FIELDS) for r in got)
+        assert len(set(size_of.calls)) == len(size_of.calls), "size_of is called at most once per GOP and q"
+        for k, r in enumerate(got):
+            assert [c for c in size_of.calls if c[0] == k] == [(k, q) for q, _ in r["trials"]]
+            assert 1 <= len(r["trials"]) <= kw["max_trials"]
+            assert (r["q_index"], r["bits"]) in r["trials"][-2:]
+            assert r["alloc"] == (sizes[k] * bitrate * rr.fps_fraction(fps).denominator) // rr.fps_fraction(fps).numerator
+        start = got[0]["trials"][0][0]
+        assert start == (choices[n // 2] if kw["q_start"] is None else kw["q_start"])
+        for prev, r in zip(got, got[1:]):
+            assert r["trials"][0][0] == prev["q_index"], "a GOP starts where the one before it ended"
+            assert r["budget"] == r["alloc"] + prev["credit"]
+            carried += prev["credit"] > 0
+        # the stated invariant: while every GOP fits, credit >= 0 and every prefix keeps to its allocations
+        bits = alloc = 0
+        for r in got:
+            if not r["fits"]:
+                break
+            bits, alloc = bits + r["bits"], alloc + r["alloc"]
+            assert r["credit"] >= 0 and bits <= alloc
+            assert r["credit"] <= (bitrate * kw["bucket_ms"]) // 1000
+        if all(r["fits"] for r in got):
+            all_fit += 1
+        else:
+            some_miss += 1
+    assert all_fit > 300 and some_miss > 300 and carried > 300, (all_fit, some_miss, carried)
+
+
+def test_controller_refusals_name_the_argument():
+    ok = dict(gop_sizes=[4, 2, 1], size_of=lambda k, q: 1000, bitrate=10 ** 6, fps=30)
+    assert len(pmctf_rate.run_controller(**ok)) == 3
+    for name, values in (("bitrate", (0, -1, 1.5, None, True, "1M")), ("fps", (0, -30, 29.97, (30, 0), (0, 1), (30,), None)),
+                         ("q_choices", ((), (3, 3), (5, 4), (0, 21), (-1, 0), (1.0, 2), 7, None)),
+                         ("q_start", (21, -1, 3.0)), ("bucket_ms", (-1, 1.5, None)), ("max_trials", (0, -1, 2.0, None)),
+                         ("slack", (1, 1.5, -0.1, None, "0")), ("gop_sizes", ([0], [4, 1.0]))):
+        for v in values:
+            with pytest.raises(ValueError, match=name):
+                pmctf_rate.run_controller(**dict(ok, **{name: v}))
+    with pytest.raises(ValueError, match="q_start"):
+        pmctf_rate.run_controller(**dict(ok, q_choices=(0, 7, 14), q_start=3))
+    c = lambda **kw: pmctf_rate.choose_q(**dict(dict(size_of=lambda q: 5, q_choices=(0, 7), start=0, budget=10), **kw))
+    assert c()["q_index"] == 7
+    for name, values in (("start", (2, -1, 0.0, None)), ("budget", (1.5, None)), ("max_trials", (0,)), ("slack", (1.0,)),
+                         ("q_choices", ((7, 0),))):
+        for v in values:
+            with pytest.raises(ValueError, match=name):
+                c(**{name: v})
+    with pytest.raises(ValueError, match="size_of"):
+        c(size_of=lambda q: 1.5)
+    for name, kw in (("gops", dict(gops=[{"first": 0}])), ("gops", dict(gops=[{"size": 0}])), ("bitrate", dict(bitrate=0)),
+                     ("fps", dict(fps=(1, 2, 3)))):
+        with pytest.raises(ValueError, match=name):
+            pmctf_rate.gop_allocations(**dict(dict(gops=[{"size": 4}], bitrate=1000, fps=30), **kw))
+
+
+# -------------------------------------------------------------------------------------------------------------- the header
+def _gops(qs=(9, 12, 3)):
+    gops = [{"first": 0, "size": 4, "me_downsample": 1, "psize": 128}, {"first": 4, "size": 2, "me_downsample": 4, "psize": 256},
+            {"first": 6, "size": 1, "me_downsample": 1, "psize": 128}]
+    return gops if qs is None else [dict(g, q_index=q) for g, q in zip(gops, qs)]
+
+
+def _fields(qs=(9, 12, 3), **over):
+    f = dict(width=132, height=100, frame_num=7, max_gop=4, q_index=3 if qs is None else qs[0], num_me_stages=1,
+             ll_order="plane", precision="f32", aten_threads=1, gops=_gops(qs))
+    f.update(over)
+    return f
+
+
+def test_version_2_round_trip_and_gop_q_indexes(tmp_path):
+    folder = str(tmp_path)
+    path = pmctf_seq.write_gop_structure(folder, **_fields())
+    want = dict(_fields(), format_version=2)
+    assert json.load(open(path)) == want and pmctf_seq.read_gop_structure(folder) == want
+    assert all(tuple(sorted(g)) == tuple(sorted(pmctf_seq.GOP_FIELDS + ("q_index",))) for g in want["gops"])
+    header, layout = pmctf_gop.sequence_layout(folder)
+    assert header == want and layout == [(0, 4, 128, 1), (4, 2, 256, 4), (6, 1, 128, 1)], "the 4-tuples stay"
+    assert pmctf_gop.gop_q_indexes(header, 3) == [9, 12, 3]
+    # every q_index of 0..20
+    for q in (0, 20):
+        pmctf_seq.write_gop_structure(folder, **_fields(qs=(q, 20 - q, q)))
+        assert pmctf_gop.gop_q_indexes(pmctf_seq.read_gop_structure(folder), 3) == [q, 20 - q, q]
+    # version 1: one q_index for all
+    pmctf_seq.write_gop_structure(folder, **_fields(qs=None, q_index=5))
+    header, layout = pmctf_gop.sequence_layout(folder)
+    assert header["format_version"] == 1 and pmctf_gop.gop_q_indexes(header, len(layout)) == [5, 5, 5]
+    # a sequence.json folder
+    old = str(tmp_path / "old")
+    os.makedirs(old)
+    pmctf_gop.write_sequence_header(old, width=132, height=100, frame_num=8, gop=4, q_index=11, psize=128, me_downsample=1,
+                                    num_me_stages=1, ll_order="plane", precision="f32", aten_threads=1)
+    header, layout = pmctf_gop.sequence_layout(old)
+    assert pmctf_gop.gop_q_indexes(header, len(layout)) == [11, 11]
+
+
+def test_version_1_is_written_and_read_as_before(tmp_path):
+    folder = str(tmp_path)
+    path = pmctf_seq.write_gop_structure(folder, **_fields(qs=None))
+    want = dict(_fields(qs=None), format_version=1)
+    assert json.load(open(path)) == want and pmctf_seq.read_gop_structure(folder) == want
+    assert open(path).read() == json.dumps(want, indent=1, sort_keys=True) + "\n", "the bytes of the file"
+    assert pmctf_seq.GOP_STRUCTURE_VERSION == 1 and pmctf_seq.GOP_FIELDS == ("first", "size", "me_downsample", "psize")
+    assert pmctf_seq.STRUCTURE_FIELDS == ("width", "height", "frame_num", "max_gop", "q_index", "num_me_stages", "ll_order",
+                                          "precision", "aten_threads", "gops")
+    # a version-1 top-level q_index is not tied to anything
+    pmctf_seq.write_gop_structure(folder, **_fields(qs=None, q_index=17))
+    assert pmctf_seq.read_gop_structure(folder)["q_index"] == 17
+
+
+def test_version_2_refusals(tmp_path):
+    folder = str(tmp_path)
+    path = os.path.join(folder, "gop_structure.json")
+
+    def refused(record):
+        open(path, "w").write(json.dumps(record))
+        with pytest.raises(ValueError) as e:
+            pmctf_seq.read_gop_structure(folder)
+        assert path in str(e.value)
+        with pytest.raises(ValueError):
+            pmctf_gop.sequence_layout(folder)
+        return str(e.value)
+
+    good = dict(_fields(), format_version=2)
+    open(path, "w").write(json.dumps(good))
+    assert pmctf_seq.read_gop_structure(folder) == good
+    assert "format version 2" in refused(dict(good, gops=_gops(None)))                       # entries without q_index
+    assert "format version 1" in refused(dict(good, format_version=1))                       # version 1 with q_index
+    assert "version" in refused(dict(good, format_version=3))
+    assert "version" in refused(dict(good, format_version=0))
+    assert "version" in refused(dict(good, format_version="2"))
+    mixed = _gops()
+    del mixed[1]["q_index"]
+    assert "format version 2" in refused(dict(good, gops=mixed))
+    assert "q_index" in refused(dict(good, gops=_gops((9, 21, 3))))
+    assert "q_index" in refused(dict(good, gops=_gops((9, -1, 3))))
+    assert "integer" in refused(dict(good, gops=_gops((9, 12.0, 3))))
+    assert "integer" in refused(dict(good, gops=_gops((9, True, 3))))
+    assert "first GOP" in refused(dict(good, q_index=12))                                    # not gops[0]'s
+    assert "holds exactly" in refused(dict(good, gops=[dict(g, qp=1) for g in _gops()]))
+    assert "first" in refused(dict(good, gops=[dict(g, first=g["first"] + 1) for g in _gops()]))   # version 1's checks hold
+    # the writer refuses the same, and a mixed list
+    os.remove(path)
+    for bad in (dict(gops=mixed), dict(gops=_gops((9, 21, 3))), dict(q_index=12), dict(gops=_gops((9, 12.5, 3)))):
+        with pytest.raises(ValueError):
+            pmctf_seq.write_gop_structure(folder, **_fields(**bad))
+    with pytest.raises(ValueError, match="version"):
+        pmctf_seq.write_gop_structure(folder, **_fields(gops=mixed))
+    assert not os.path.exists(path)
+
+
+# ------------------------------------------------------------------------------------------------------ the record checker
+SIZES = (4, 2, 1)
+CHOICES = (0, 7, 14, 20)
+TABLE = [[8 * v for v in row] for row in ((500, 900, 1500, 2600), (260, 470, 800, 1300), (400, 450, 420, 700))]   # bits
+PARAMS = dict(bitrate=72000, fps=30, q_choices=CHOICES, q_start=7, bucket_ms=25, max_trials=3, slack=0.0)
+
+
+def _dummy_folder(folder):
+    """a folder as encode_sequence_rate leaves it, its bitstream files filled with zeros of the controller's sizes"""
+    os.makedirs(folder)
+    records = pmctf_rate.run_controller(SIZES, lambda k, q: TABLE[k][CHOICES.index(q)], **PARAMS)
+    for k, (size, r) in enumerate(zip(SIZES, records)):
+        sub = os.path.join(folder, pmctf_gop.gop_folder(k))
+        os.makedirs(sub)
+        names = pmctf_gop.gop_file_names(size) if size > 1 else ["0_main.bin", "0_C_main.bin"]
+        left = r["bits"] // 8
+        for i, name in enumerate(names):
+            n = left if i == len(names) - 1 else left // 3
+            open(os.path.join(sub, name), "wb").write(bytes(n))
+            left -= n
+    gops = [dict(g, me_downsample=1, psize=128, q_index=r["q_index"]) for g, r in zip(_gops(None), records)]
+    pmctf_seq.write_gop_structure(folder, **_fields(gops=gops, q_index=gops[0]["q_index"]))
+    pmctf_rate.write_rate_record(folder, pmctf_rate.Controller(**PARAMS), records)
+    return records
+
+
+def _edit(folder, fn):
+    path = os.path.join(folder, "rate_control.json")
+    rec = json.load(open(path))
+    fn(rec)
+    json.dump(rec, open(path, "w"))
+
+
+def test_verify_rate_record(tmp_path):
+    folder = str(tmp_path / "bins")
+    records = _dummy_folder(folder)
+    # worked by hand: alloc 9600, 4800, 2400 and a bucket of 1800 bits.  GOP 0: 7200 at q 7 fits, 12000 at 14 does not;
+    # 2400 are left, 1800 carried.  GOP 1: budget 6600; 3760 and 6400 fit, 10400 does not, the trials are used up; 200
+    # carried.  GOP 2: budget 2600; 3360 at 14, 3600 at 7 and 3200 at 0 all miss: the last is taken, the credit goes to -600
+    assert records == rr.run(SIZES, lambda k, q: TABLE[k][CHOICES.index(q)], **PARAMS)
+    assert [r["q_index"] for r in records] == [7, 14, 0] and [r["fits"] for r in records] == [True, True, False]
+    assert [r["budget"] for r in records] == [9600, 6600, 2600] and [r["credit"] for r in records] == [1800, 200, -600]
+    assert [len(r["trials"]) for r in records] == [2, 3, 3]
+    v = pmctf_rate.verify_rate_record(folder)
+    assert v["frame_num"] == 7 and v["total_bits"] == sum(r["bits"] for r in records)
+    assert v["bits_per_second"] == v["total_bits"] * 30 / 7
+    assert v["record"]["gops"] == json.loads(json.dumps(records)) and v["record"]["bucket_bits"] == 1800
+    assert v["record"]["format_version"] == 1 and v["record"]["fps"] == [30, 1]
+    assert v["header"] == pmctf_seq.read_gop_structure(folder)
+    keep = {n: open(os.path.join(folder, n)).read() for n in ("rate_control.json", "gop_structure.json")}
+
+    def caught(match, restore=lambda: None):
+        with pytest.raises(ValueError, match=match) as e:
+            pmctf_rate.verify_rate_record(folder)
+        assert os.path.join(folder, "rate_control.json") in str(e.value)
+        for n, text in keep.items():
+            open(os.path.join(folder, n), "w").write(text)
+        restore()
+        pmctf_rate.verify_rate_record(folder)
+
+    # a resized file
+    victim = os.path.join(folder, "gop_00001", "1_mv.bin")
+    data = open(victim, "rb").read()
+    for resized in (data + b"\0", data[:-1]):
+        open(victim, "wb").write(resized)
+        caught("GOP 1: bits", lambda: open(victim, "wb").write(data))
+    os.remove(victim)
+    caught("GOP 1.*missing", lambda: open(victim, "wb").write(data))
+    # a wrong credit, at the GOP and carried into the next budget
+    _edit(folder, lambda rec: rec["gops"][0].update(credit=2400))
+    caught("GOP 0: credit")
+    _edit(folder, lambda rec: rec["gops"][2].update(budget=rec["gops"][2]["budget"] + 8))
+    caught("GOP 2: budget")
+    _edit(folder, lambda rec: rec["gops"][1].update(alloc=rec["gops"][1]["alloc"] + 1))
+    caught("GOP 1: alloc")
+    # a wrong fits
+    _edit(folder, lambda rec: rec["gops"][1].update(fits=False))
+    caught("GOP 1: fits")
+    _edit(folder, lambda rec: rec["gops"][2].update(fits=True))
+    caught("GOP 2: fits")
+    # a header q that differs from the record
+    head = pmctf_seq.read_gop_structure(folder)
+    head["gops"][2]["q_index"] = 7
+    pmctf_seq.write_gop_structure(folder, **{k: head[k] for k in pmctf_seq.STRUCTURE_FIELDS})
+    caught("GOP 2: q_index")
+    _edit(folder, lambda rec: rec["gops"][1].update(q_index=20))
+    caught("GOP 1: q_index")
+    # an accepted trial that was never run, parameters that give another bucket, a version-1 header, no record
+    _edit(folder, lambda rec: rec["gops"][0].update(trials=[[14, 12000]]))
+    caught("GOP 0: .*trials")
+    _edit(folder, lambda rec: rec.update(bucket_ms=50))
+    caught("bucket_bits")
+    _edit(folder, lambda rec: rec.update(format_version=2))
+    caught("version")
+    _edit(folder, lambda rec: rec.pop("slack"))
+    caught("missing")
+    _edit(folder, lambda rec: rec["gops"].pop())
+    caught("2 GOP records")
+    pmctf_seq.write_gop_structure(folder, **_fields(qs=None))
+    caught("version 1")
+    os.remove(os.path.join(folder, "rate_control.json"))
+    with pytest.raises(ValueError, match="rate_control.json: missing"):
+        pmctf_rate.verify_rate_record(folder)
+
+
+def test_check_rate_tool(tmp_path, capsys):
+    folder = str(tmp_path / "bins")
+    records = _dummy_folder(folder)
+    spec = importlib.util.spec_from_file_location("check_rate", os.path.join(ROOT, "tools", "check_rate.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    assert tool.main([folder]) == 0
+    out = capsys.readouterr().out
+    lines = out.strip().split("\n")
+    assert len(lines) == 5
+    for k, r in enumerate(records):
+        cells = lines[1 + k].split()
+        assert cells[:7] == [str(k), str(sum(SIZES[:k])), str(SIZES[k]), str(r["q_index"]), str(r["bits"]), str(r["budget"]),
+                             str(r["credit"])]
+    total = sum(r["bits"] for r in records)
+    assert f"{total} bits: {total * 30 / 7:.0f} bits per second, target 72000; 1 of 3 GOPs over" in lines[4]
+    open(os.path.join(folder, "gop_00000", "0_main.bin"), "ab").write(b"\0\0")
+    assert tool.main([folder]) == 1
+    assert "GOP 0: bits" in capsys.readouterr().out
+
+
+# ------------------------------------------------------------------------------------------------------------ the encoder
+def test_public_signatures():
+    p = inspect.signature(pmctf_rate.encode_sequence_rate).parameters
+    g = inspect.signature(pmctf_seq.encode_sequence_gops).parameters
+    c = inspect.signature(pmctf_rate.run_controller).parameters
+    names = list(g)
+    at = names.index("q_index")
+    assert list(p) == names[:at] + ["bitrate", "fps"] + names[at + 1:] + list(c)[4:]
+    assert list(c) == ["gop_sizes", "size_of", "bitrate", "fps", "q_choices", "q_start", "bucket_ms", "max_trials", "slack"]
+    for k in list(c)[4:]:
+        assert p[k].default == c[k].default, k
+    assert (c["q_choices"].default, c["q_start"].default, c["bucket_ms"].default, c["max_trials"].default,
+            c["slack"].default) == (range(21), None, 1000, 4, 0.0)
+    for k in ("structure", "ds_factors", "skip_decoding", "psize", "src_format", "ingest", "decoded_frame_path", "picture_hash",
+              "bitdepth", "msssim"):
+        assert p[k].default == g[k].default, k
+    assert list(inspect.signature(pmctf_rate.choose_q).parameters) == ["size_of", "q_choices", "start", "budget",
+                                                                       "max_trials", "slack"]
+    assert list(inspect.signature(pmctf_rate.gop_allocations).parameters) == ["gops", "bitrate", "fps"]
+    assert list(inspect.signature(pmctf_rate.verify_rate_record).parameters) == ["bin_folder"]
+    assert list(inspect.signature(pmctf_gop.gop_q_indexes).parameters) == ["header", "n_gops"]
+    from pMCTF.models.pWave import pWave
+    assert pWave.get_qp_num() == pmctf_rate.Q_NUM == pmctf_seq.Q_NUM == 21
+
+
+def test_encode_refusals_come_before_the_codec_is_touched(tmp_path):
+    class NoDevice:
+        def __getattr__(self, name):
+            raise AssertionError(f"the codec was touched ({name}) before the arguments were checked")
+
+    def call(frame_num=7, max_gop=4, bitrate=10 ** 5, fps=30, device="cuda", **kw):
+        return pmctf_rate.encode_sequence_rate(NoDevice(), str(tmp_path / "none.yuv"), 132, 100, frame_num, max_gop, bitrate,
+                                               fps, str(tmp_path), device, **kw)
+    with pytest.raises(ValueError, match="search"):
+        call(structure="search", max_gop=8)
+    for name, v in (("bitrate", 0), ("bitrate", 1e5), ("fps", 0), ("fps", 29.97), ("fps", (30000, 0))):
+        with pytest.raises(ValueError, match=name):
+            call(**{name: v})
+    for name, v in (("q_choices", (7, 0)), ("q_choices", (0, 21)), ("q_choices", ()), ("q_start", 21), ("bucket_ms", -1),
+                    ("max_trials", 0), ("slack", 1.0), ("slack", -0.5)):
+        with pytest.raises(ValueError, match=name):
+            call(**{name: v})
+    with pytest.raises(ValueError, match="q_start"):
+        call(q_choices=(0, 7, 14, 20), q_start=3)
+    # encode_sequence_gops' own refusals hold
+    for n in (0, -3, 7.0):
+        with pytest.raises(ValueError, match="frame_num"):
+            call(frame_num=n)
+    for g in (1, 3, 6):
+        with pytest.raises(ValueError, match="max_gop"):
+            call(max_gop=g)
+    with pytest.raises(ValueError, match="structure"):
+        call(structure="adaptive")
+    for listed in ([(4, 1), (2, 1)], [(4, 1), (3, 1)], []):
+        with pytest.raises(ValueError):
+            call(structure=listed)
+    with pytest.raises(ValueError, match="bitdepth 10"):
+        call(bitdepth=10, picture_hash="u8")
+    with pytest.raises(ValueError, match="bitdepth 8"):
+        call(picture_hash="u16")
+    with pytest.raises(ValueError):
+        call(ingest="gpu")
+    with pytest.raises(RuntimeError, match="encode_sequence_rate.*GPU"):              # no CPU fallback
+        call(structure="scenecut", device="cpu")
+    assert os.listdir(tmp_path) == []
+
+
+class FakeCodec:
+    """stands in for the model where only the folders matter: a lone picture "codes" to files of a size per q_index"""
+    num_me_stages = 1
+
+    def __init__(self, bin_folder, bytes_of, fail_at=None):
+        self.bin_folder, self.bytes_of, self.fail_at, self.seen = bin_folder, bytes_of, fail_at, []
+
+    def engine(self):
+        import types
+        return types.SimpleNamespace(precision="f32", aten_threads=1)
+
+    def encode_lone_picture(self, frame, output_folder, pic_width, pic_height, psize=128, skip_decoding=True, q_index=0):
+        assert os.path.isdir(output_folder)
+        self.seen.append((q_index, sorted(os.listdir(self.bin_folder))))
+        if len(self.seen) == self.fail_at:
+            raise RuntimeError("the coder failed")
+        n = self.bytes_of[q_index]
+        open(os.path.join(output_folder, "0_main.bin"), "wb").write(bytes(n - 1))
+        open(os.path.join(output_folder, "0_C_main.bin"), "wb").write(bytes(1))
+        return {"L_t": frame[0], "L_tc": frame[1], "bit_L": 8.0 * n, "bit_Lc": 8.0, "encoding_time": 0.0, "decoding_time": 0.0}
+
+
+def test_trial_folders_with_a_stand_in_codec(tmp_path):
+    """three lone pictures: at most two trial folders of a GOP at any time, the accepted one renamed, none left, also
+    after the coder raises; the record is the restatement's"""
+    import pmctf_synth
+    w, h = 16, 8
+    src = str(tmp_path / "src.yuv")
+    pmctf_gop.write_yuv(src, pmctf_synth.synth_yuv420(w, h, 3, seed=1))
+    bytes_of = {0: 100, 7: 200, 14: 300, 20: 400}
+    params = dict(q_choices=(0, 7, 14, 20), q_start=0, bucket_ms=10 ** 6, max_trials=4, slack=0.0)
+    want = rr.run((1, 1, 1), lambda k, q: 8 * bytes_of[q], 8 * 260, 1, **params)
+    assert [(r["q_index"], len(r["trials"])) for r in want] == [(7, 3), (14, 3), (7, 2)]    # up, up on credit, down
+
+    def run(folder, fail_at=None):
+        bins = str(tmp_path / folder)
+        os.makedirs(bins)
+        codec = FakeCodec(bins, bytes_of, fail_at)
+        call = lambda: pmctf_rate.encode_sequence_rate(codec, src, w, h, 3, 2, 8 * 260, 1, bins, "cpu",
+                                                       structure=[(1, 1)] * 3, **params)
+        return bins, codec, call
+
+    bins, codec, call = run("good")
+    out = call()
+    assert [{f: r[f] for f in pmctf_rate.RECORD_FIELDS} for r in out["rate"]] == want
+    assert [q for q, _ in codec.seen] == [q for r in want for q, _ in r["trials"]]
+    for q, names in codec.seen:
+        trials = [n for n in names if n.endswith(".trial")]
+        assert len(trials) <= 2 and sum(n.endswith(f".q{q:02d}.trial") for n in trials) == 1, names
+    # GOP 0: when 14 is tried only 7 (the best) is kept beside it, 0 is gone
+    assert codec.seen[2] == (14, ["gop_00000.q07.trial", "gop_00000.q14.trial"])
+    # GOP 2, descending: nothing fits yet, so only the newest is there beside the finished GOPs
+    assert codec.seen[7] == (7, ["gop_00000", "gop_00001", "gop_00002.q07.trial"])
+    assert sorted(os.listdir(bins)) == ["gop_00000", "gop_00001", "gop_00002", "gop_structure.json", "rate_control.json"]
+    assert [os.path.getsize(os.path.join(bins, f"gop_0000{k}", "0_main.bin")) + 1 for k in range(3)] == [200, 300, 200]
+    assert [g["q_index"] for g in out["gops"]] == [7, 14, 7] and out["bits"] == [1600.0, 2400.0, 1600.0]
+    pmctf_rate.verify_rate_record(bins)
+    # the same folder again: the GOP folders of the earlier run are replaced
+    assert [g["q_index"] for g in call()["gops"]] == [7, 14, 7]
+    pmctf_rate.verify_rate_record(bins)
+    for fail_at in (1, 2, 3, 5, 8):
+        bins, codec, call = run(f"fails_at_{fail_at}", fail_at)
+        with pytest.raises(RuntimeError, match="the coder failed"):
+            call()
+        left = sorted(os.listdir(bins))
+        assert not any(n.endswith(".trial") for n in left), left
+        assert left == [f"gop_0000{k}" for k in range((0, 0, 0, 1, 1, 2, 2, 2)[fail_at - 1])]
+
+
+def test_tool_argument_refusals(tmp_path, capsys):
+    spec = importlib.util.spec_from_file_location("encode_sequence_tool", os.path.join(ROOT, "tools", "encode_sequence.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    assert tool.parse_fps("30") == (30, 1) and tool.parse_fps("30000/1001") == (30000, 1001)
+    base = ["--synth-seed", "0", "--width", "132", "--height", "100", str(tmp_path / "none.yuv"), str(tmp_path / "bins")]
+
+    def refused(*args):
+        with pytest.raises(SystemExit) as e:
+            tool.main(list(args) + base)
+        assert e.value.code == 2
+        return capsys.readouterr().err
+
+    rate = ("--bitrate", "100000", "--fps", "30")
+    assert "search" in refused(*rate, "--structure", "search")
+    assert "--fps" in refused("--bitrate", "100000")
+    for option, value in (("--fps", "30"), ("--bucket-ms", "500"), ("--max-trials", "2"), ("--slack", "0.1"), ("--q-min", "2"),
+                          ("--q-max", "9")):
+        assert f"{option}: only with --bitrate" in refused(option, value)
+    assert "bitrate" in refused("--bitrate", "0", "--fps", "30")
+    assert "fps" in refused("--bitrate", "100000", "--fps", "0")
+    assert "fps" in refused("--bitrate", "100000", "--fps", "30/0")
+    assert "--fps" in refused("--bitrate", "100000", "--fps", "29.97")
+    assert "q-min" in refused(*rate, "--q-min", "9", "--q-max", "5")
+    assert "q-max" in refused(*rate, "--q-max", "21")
+    assert "q-min" in refused(*rate, "--q-min", "-1")
+    assert "q_start" in refused(*rate, "--q-min", "5", "--q-index", "3")
+    assert "max_trials" in refused(*rate, "--max-trials", "0")
+    assert "slack" in refused(*rate, "--slack", "1")
+    assert "bucket_ms" in refused(*rate, "--bucket-ms", "-5")
+    assert not os.path.exists(tmp_path / "bins")

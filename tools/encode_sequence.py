@@ -19,7 +19,12 @@ rate-distortion search per window of --gop pictures.  The chosen list and the cu
 gop_structure.json instead of sequence.json, which tools/decode_sequence.py reads as well.
 --layer-hashes: after the encode the folder is decoded once more (pmctf_layers.write_layer_hashes, checked against the
 picture hashes where there are any) and BIN_FOLDER/layer_hashes.json records the CRC-32 of every picture of every temporal
-layer, which tools/decode_sequence.py --temporal-level K checks."""
+layer, which tools/decode_sequence.py --temporal-level K checks.
+--bitrate BITS_PER_S --fps N[/D] (pmctf_rate.encode_sequence_rate): instead of one --q-index for the sequence every GOP gets
+its own, chosen from --q-min..--q-max by coding the GOP up to --max-trials times so that the sequence keeps to the bitrate
+(--bucket-ms: how much unspent rate is carried on; --slack: stop raising q_index within that fraction of the budget;
+--q-index, when given, is where the first GOP starts).  The structure is fill (the default here) or scenecut; search is
+refused.  BIN_FOLDER gets rate_control.json, which tools/check_rate.py checks without a GPU; the choices go to stderr."""
 import argparse
 import os
 import sys
@@ -28,7 +33,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "learned-pmctf_amd"))
 
 
-def main():
+def parse_fps(text):
+    """N or N/D -> (N, D)"""
+    num, _, den = text.partition("/")
+    try:
+        return int(num), int(den) if den else 1
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"N or N/D, positive integers (got {text!r})") from None
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     w = ap.add_mutually_exclusive_group(required=True)
     w.add_argument("--checkpoint", help="weights file (torch.save of a state_dict, or of a dict holding one)")
@@ -41,7 +55,14 @@ def main():
     ap.add_argument("--hd-min", type=float, help="scenecut: least histogram change, 0..1 (default: pmctf_seq.HD_MIN)")
     ap.add_argument("--mad-min", type=float,
                     help="scenecut: least mean absolute luma difference, 8-bit units (default: pmctf_seq.MAD_MIN)")
-    ap.add_argument("--q-index", type=int, default=3)
+    ap.add_argument("--q-index", type=int, help="default 3; with --bitrate: the q_index the first GOP starts from")
+    ap.add_argument("--bitrate", type=int, metavar="BITS_PER_S", help="code to this bitrate, a q_index per GOP (needs --fps)")
+    ap.add_argument("--fps", type=parse_fps, metavar="N[/D]", help="pictures per second of the source, such as 30 or 30000/1001")
+    ap.add_argument("--bucket-ms", type=int, help="--bitrate: unspent rate carried on, in milliseconds of the bitrate (1000)")
+    ap.add_argument("--max-trials", type=int, help="--bitrate: codings of one GOP at the most (4)")
+    ap.add_argument("--slack", type=float, help="--bitrate: a GOP within this fraction of its budget is not tried higher (0)")
+    ap.add_argument("--q-min", type=int, help="--bitrate: the lowest q_index to choose from (0)")
+    ap.add_argument("--q-max", type=int, help="--bitrate: the highest q_index to choose from (20)")
     ap.add_argument("--frames", type=int, help="pictures to code (default: all whole GOPs of the source)")
     ap.add_argument("--width", type=int, help="picture width (.yuv sources)")
     ap.add_argument("--height", type=int, help="picture height (.yuv sources)")
@@ -55,7 +76,34 @@ def main():
                     help="also record the hashes of the temporal layers (layer_hashes.json), from a full decode of the folder")
     ap.add_argument("source", help=".yuv file or folder of PNGs")
     ap.add_argument("bin_folder")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    rate_options = {k: getattr(a, k) for k in ("fps", "bucket_ms", "max_trials", "slack", "q_min", "q_max")}
+    rate = None
+    if a.bitrate is None:
+        given = ["--" + k.replace("_", "-") for k, v in rate_options.items() if v is not None]
+        if given:
+            ap.error(f"{', '.join(given)}: only with --bitrate")
+        if a.q_index is None:
+            a.q_index = 3
+    else:
+        import pmctf_rate
+        if a.structure == "search":
+            ap.error("--bitrate with --structure search: the search ranks GOP sizes at one fixed q_index")
+        if a.fps is None:
+            ap.error("--bitrate needs --fps")
+        q_min = 0 if a.q_min is None else a.q_min
+        q_max = pmctf_rate.Q_NUM - 1 if a.q_max is None else a.q_max
+        rate = dict(q_choices=range(q_min, q_max + 1), q_start=a.q_index,
+                    bucket_ms=1000 if a.bucket_ms is None else a.bucket_ms,
+                    max_trials=4 if a.max_trials is None else a.max_trials, slack=0.0 if a.slack is None else a.slack)
+        try:
+            if not 0 <= q_min <= q_max < pmctf_rate.Q_NUM:
+                raise ValueError(f"--q-min {q_min} and --q-max {q_max}: 0 <= q-min <= q-max <= {pmctf_rate.Q_NUM - 1}")
+            pmctf_rate.Controller(a.bitrate, a.fps, **rate)               # the arguments, checked before anything is loaded
+        except ValueError as e:
+            ap.error(str(e))
+        if a.structure == "fixed":
+            a.structure = "fill"
     import torch
     import pmctf_gop
     from pMCTF.models.video.pMCTF_L import pMCTF
@@ -103,10 +151,18 @@ def main():
                                             keep_gops=True, **common)
         else:
             import pmctf_seq
-            out = pmctf_seq.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
-                                                 a.device, structure=a.structure,
-                                                 hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
-                                                 mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min, **common)
+            cuts = dict(structure=a.structure, hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
+                        mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min)
+            if rate is not None:
+                out = pmctf_rate.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
+                                                      a.bin_folder, a.device, **cuts, **common, **rate)
+                for k, r in enumerate(out["rate"]):
+                    print(f"GOP {k}: q_index {r['q_index']}, {r['bits']} bits of {r['budget']}"
+                          f"{'' if r['fits'] else ' (does not fit)'}, {len(r['trials'])} trial(s), credit {r['credit']}",
+                          file=sys.stderr)
+            else:
+                out = pmctf_seq.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                                                     a.device, **cuts, **common)
             if "cuts" in out:
                 print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
             print("GOPs (first picture: size, motion down-sampling): " +
