@@ -477,6 +477,31 @@ int pmctf_frame_sse_u16_f32(const float *rec_y, const float *rec_c, const float 
                             int h, int w, int bitdepth, uint64_t *sse3, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Resampling of 4:2:0 pictures (csrc/picture_scale.hip): one packed planar picture of h_in x w_in (h_in*w_in luma samples,
+ * then two planes of (h_in/2)*(w_in/2), as it lies in a .yuv file) -> one of h_out x w_out, by the separable Catmull-Rom
+ * bicubic with antialiasing stretch and 14-bit integer coefficients of DESIGN 5l.  Bytes for the u8 entry (bitdepth 8),
+ * 16-bit samples of bitdepth 9..16 for the u16 entry; max = 2^bitdepth - 1.
+ *   luma_x, luma_y, chroma_x, chroma_y: the tables of the four axes (w_in -> w_out, h_in -> h_out and the same of the
+ *   halved sizes), built on the host (pmctf_scale.axis_table), in DEVICE memory, 4-byte aligned.  A table of n_out rows of
+ *   T taps is int32 start[n_out] followed by int16 coef[n_out][T]; every row sums to 16384 and rows shorter than T are
+ *   zero-filled.  taps: the four T in that order, an array on the HOST, each 1..20.
+ *   Per plane: t = (sum_k coef_x[ox][k] * src[r][min(start_x[ox] + k, w_in - 1)] + 32) >> 6 (arithmetic shift, int32), then
+ *   out = clamp((sum_k coef_y[oy][k] * t[min(start_y[oy] + k, h_in - 1)][ox] + 2^21) >> 22, 0, max) in 64-bit integers.
+ *   Integer sums: the result does not depend on the order of summation and is the same on every run.  Every index taken
+ *   from a table is clamped before use; start must not decrease along a table (the kernel takes a tile's source rows
+ *   from its first and last row).
+ * One launch for the three planes, nothing intermediate in global memory, no synchronisation.  PMCTF_EINVAL, before the
+ * launch and with dst untouched, for a null pointer, a size that is odd, not positive or above 16384, h_out / h_in or
+ * w_out / w_in outside [1/4, 4], a tap count outside 1..20, a bitdepth the entry does not take, src or dst less aligned
+ * than a sample, a table less aligned than 4 bytes. */
+int pmctf_resize_yuv420_u8(const uint8_t *src, uint8_t *dst, int h_in, int w_in, int h_out, int w_out, const void *luma_x,
+                           const void *luma_y, const void *chroma_x, const void *chroma_y, const int taps[4], int bitdepth,
+                           void *stream);
+int pmctf_resize_yuv420_u16(const uint16_t *src, uint16_t *dst, int h_in, int w_in, int h_out, int w_out, const void *luma_x,
+                            const void *luma_y, const void *chroma_x, const void *chroma_y, const int taps[4], int bitdepth,
+                            void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Sequence structure pre-analysis (csrc/scene_ops.hip): the luma histogram of one picture and its sum of absolute
  * differences against the previous one, the figures pmctf_seq.scene_cuts decides scene changes from.
  *

@@ -771,6 +771,42 @@ def frame_sse_hbd(rec_y, rec_c, org_y, org_c, h, w, bitdepth):
 
 
 # ------------------------------------------------------------------------------------------------
+# resampling of packed 4:2:0 pictures (csrc/picture_scale.hip)
+def resize_yuv420(frame, h_in, w_in, h_out, w_out, tables, taps, bitdepth=8):
+    """One packed planar 4:2:0 picture (uint8 device tensor of h_in*w_in*3/2 bytes at bitdepth 8, uint16 of as many samples
+    at 9..16) -> the packed picture of h_out x w_out, same type: the integer Catmull-Rom resampling of DESIGN 5l.
+    tables: the four axis tables (luma x, luma y, chroma x, chroma y) as uint8 device tensors in the layout
+    pmctf_scale.device_table uploads, taps: their four tap counts.  One launch."""
+    h_in, w_in = _picture_size(h_in, w_in)
+    h_out, w_out = _picture_size(h_out, w_out)
+    bitdepth = int(bitdepth)
+    dtype = torch.uint8 if bitdepth == 8 else torch.uint16
+    if bitdepth != 8:
+        _bitdepth(bitdepth)
+    if 4 * h_out < h_in or h_out > 4 * h_in or 4 * w_out < w_in or w_out > 4 * w_in:
+        raise ValueError(f"{h_in}x{w_in} -> {h_out}x{w_out}: the sizes differ by more than a factor of 4 on an axis")
+    if not isinstance(frame, torch.Tensor) or frame.dtype != dtype:
+        raise ValueError(f"expect a {dtype} tensor at bitdepth {bitdepth}")
+    if frame.numel() != h_in * w_in * 3 // 2:
+        raise ValueError(f"a {h_in}x{w_in} 4:2:0 picture has {h_in * w_in * 3 // 2} samples, got {frame.numel()}")
+    dev = _dev(frame)
+    frame = frame.contiguous()
+    taps = [int(t) for t in taps]
+    if len(tables) != 4 or len(taps) != 4:
+        raise ValueError("expect four tables and four tap counts: luma x, luma y, chroma x, chroma y")
+    for t, n_out, n in zip(tables, (w_out, h_out, w_out // 2, h_out // 2), taps):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not 1 <= n <= 20 or t.numel() != n_out * (4 + 2 * n):
+            raise ValueError(f"a table of {n_out} rows of {n} taps is a uint8 tensor of {n_out * (4 + 2 * n)} bytes, 1..20 taps")
+        if _dev(t) != dev:
+            raise ValueError("the tables live on the picture's device")
+    out = torch.empty(h_out * w_out * 3 // 2, dtype=dtype, device=dev)
+    fn = _lib.hip().pmctf_resize_yuv420_u8 if bitdepth == 8 else _lib.hip().pmctf_resize_yuv420_u16
+    _lib.check(fn((_pu8 if bitdepth == 8 else _pu16)(frame), C.c_void_p(out.data_ptr()), h_in, w_in, h_out, w_out,
+                  *(_pu8(t.contiguous()) for t in tables), (C.c_int * 4)(*taps), bitdepth, _stream()), "resize_yuv420")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # sequence structure pre-analysis (csrc/scene_ops.hip)
 def luma_activity(cur, prev, bitdepth=8, hist=None, sad=None):
     """The luma histogram of one picture and its sum of absolute differences against the previous one, in integers at

@@ -360,12 +360,16 @@ def read_gop_device(reader, gop, device, psize=128):
     """read_gop with the arithmetic on the device: the same triple, tensor for tensor and bit for bit.  From a YUVReader a
     picture costs one copy of its bytes to the device and one launch (pmctf_yuv420_u8_to_planes_f32: conversion, padding
     and the un-padded originals); from a PNGReader the RGB bytes are copied and converted to 4:2:0 first
-    (pmctf_rgb8_to_yuv420_u8).  A YUVReader of 16-bit samples goes through pmctf_yuv420_u16_to_planes_f32 the same way."""
+    (pmctf_rgb8_to_yuv420_u8).  A YUVReader of 16-bit samples goes through pmctf_yuv420_u16_to_planes_f32 the same way.
+    A reader with a `resample` attribute (pmctf_scale.CodedSize.ingest: a sequence coded at another size than its source's)
+    has every packed picture resampled on the device before the planes are made; the triple is then that of a source of
+    resample.shape."""
     import numpy as np
     from pMCTF.hip import ops
     _need_gpu(device, "read_gop_device")
     padded, orig, size = [], [], None
     bitdepth = getattr(reader, "bitdepth", 8)
+    resample = getattr(reader, "resample", None)
     for _ in range(gop):
         pic = reader.read_one_frame()
         assert pic is not None, "sequence ends inside a GOP"
@@ -377,13 +381,16 @@ def read_gop_device(reader, gop, device, psize=128):
             frame = torch.from_numpy(np.concatenate([p.reshape(-1) for p in pic])).to(device)
         assert size in (None, shape), "picture size changes inside the sequence"
         size = shape
+        h, w = shape
+        if resample is not None:
+            frame, (h, w) = resample(frame), resample.shape
         if bitdepth > 8:
-            y_pad, c_pad, y_org, c_org = ops.planes_from_u16(frame, size[0], size[1], bitdepth, psize=psize)
+            y_pad, c_pad, y_org, c_org = ops.planes_from_u16(frame, h, w, bitdepth, psize=psize)
         else:
-            y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, size[0], size[1], psize=psize)
+            y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, h, w, psize=psize)
         orig.append([y_org, c_org])
         padded.append([y_pad, c_pad])
-    return padded, orig, size
+    return padded, orig, size if resample is None else resample.shape
 
 
 def pngs_to_yuv(paths_or_folder, yuv_out, device):
@@ -462,7 +469,19 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     tables come from gop_quality_hbd: "psnr" is the YUV-PSNR at that depth, "psnr_rgb" 0.0 per frame; msssim=True and
     decoded_frame_path are refused (ValueError), picture_hash is "u16" or "f32".  With keep_gops=True bin_folder also gets
     picture_format.json (write_picture_format), which tells decode_sequence the depth.
+    pmctf_scale.encode_sequence(..., coded_size=(W, H)) is this function for a sequence coded at another size than its
+    source's (a pmctf_scale.CodedSize handed to the shared body): the pictures are resampled on the device after upload
+    (read_gop_device, whatever `ingest` says) and everything below sees a source of the coded size, sequence.json included;
+    with keep_gops=True bin_folder also gets display_format.json, and the result gains "display_quality".
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
+    return _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device, skip_decoding, psize,
+                            src_format, ingest, decoded_frame_path, picture_hash, bitdepth, keep_gops, msssim)
+
+
+def _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
+                     skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
+                     picture_hash=None, bitdepth=8, keep_gops=False, msssim=False, scale=None):
+    """encode_sequence's body; scale: a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence)"""
     import io
     import time
     if picture_hash is not None and picture_hash not in HASH_LEVELS:
@@ -484,7 +503,7 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     assert frame_num % gop == 0
     if src_format not in ("yuv", "png") or ingest not in ("host", "device"):
         raise ValueError(f"src_format is 'yuv' or 'png' and ingest 'host' or 'device' (got {src_format!r}, {ingest!r})")
-    on_device = src_format == "png" or ingest == "device"
+    on_device = src_format == "png" or ingest == "device" or scale is not None
     if on_device:
         _need_gpu(device, f"encode_sequence(src_format={src_format!r}, ingest={ingest!r})")
     if src_format == "png":
@@ -495,6 +514,10 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
             raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
     else:
         reader = YUVReader(yuv_path, width, height, start_index=0, bitdepth=bitdepth)
+    display = []
+    if scale is not None:
+        reader.resample = scale.ingest(keep=True)
+        width, height = scale.coded
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines = []
     ssims = []
@@ -519,6 +542,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
             rec = decode_gop(codec, enc["frames_coded"])
             report_gop(rec, orig, h, w, enc["bits"], enc["bits_mv"], first_frame, tables, ssims, hashes,
                        picture_hash=picture_hash, bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
+            if scale is not None:
+                display += scale.display_quality(rec)
     reader.close()
     if keep_gops:
         write_sequence_header(bin_folder, width=width, height=height, frame_num=frame_num, gop=gop, q_index=q_index,
@@ -528,6 +553,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
             write_picture_hashes(bin_folder, picture_hash, hashes)
         if bitdepth > 8:
             write_picture_format(bin_folder, bitdepth)
+        if scale is not None:
+            scale.write_header(bin_folder)
     for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
         lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
     record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
@@ -539,6 +566,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
         out["msssim"] = ssims
     if picture_hash is not None:
         out["picture_hashes"] = hashes
+    if scale is not None:
+        out["display_quality"] = display
     return out
 
 
@@ -1091,8 +1120,17 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     return the mismatches.  The hashes are taken on the device (picture_hashes, at the file's level) before anything of a
     GOP is written; under "auto" and True the first mismatch raises PictureHashMismatch (a ValueError naming the GOP's
     folder, the frame, the plane and both values) with none of that GOP's pictures written.
+    A folder with a display_format.json (pmctf_scale: coded at another size than its source's) has every picture resampled
+    to that display size on the device before it is written, .yuv and PNGs alike; the hashes are those of the coded-size
+    pictures and are checked before.  pmctf_scale.decode_sequence_checked(..., coded_size_output=True) writes the
+    coded-size pictures instead.
     Returns decode_sequence's dict: "verified" counts the pictures checked, "hash_mismatches" lists {"gop", "folder",
-    "frame", "plane", "decoded", "recorded"}."""
+    "frame", "plane", "decoded", "recorded"}; "frames" holds the written sizes."""
+    return _decode_sequence(codec, bin_folder, yuv_out, device, png_out, verify)
+
+
+def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", coded_size_output=False):
+    """decode_sequence_checked's body; coded_size_output: pmctf_scale.decode_sequence_checked"""
     import contextlib
     import time
     if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
@@ -1112,6 +1150,9 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
         recorded = read_picture_hashes(bin_folder, header["frame_num"])
     h, w = header["height"], header["width"]
+    import pmctf_scale
+    display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
+    out_shape = (h, w) if display is None else display.size[::-1]
     q_indexes = gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, verified = [], [], [], 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
@@ -1128,14 +1169,18 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
                 mismatches += bad
                 verified += size
             if f is not None:
-                pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
-                    frames_to_u8(out["frames"], h, w)
+                if display is not None:
+                    pictures = display.pictures(out["frames"])
+                else:
+                    pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
+                        frames_to_u8(out["frames"], h, w)
                 for planes in pictures:
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:
-                write_pngs(png_out, first, frames_to_rgb8(out["frames"], h, w))
-            shapes += [(h, w)] * size
+                write_pngs(png_out, first, frames_to_rgb8(out["frames"], h, w) if display is None else
+                           display.rgb8(out["frames"]))
+            shapes += [out_shape] * size
             seconds.append(time.time() - t0)
     return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
             "bitdepth": bitdepth}

@@ -375,8 +375,8 @@ def _check_against_extract(bin_folder, level, motion_fill):
 
 def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     """Copy what a level-`level` decode of the sequence in src_folder reads into dst_folder (created when missing; refused
-    when not empty): the header, picture_format.json and layer_hashes.json where present, per GOP exactly
-    layer_file_names(size, level, motion_fill), and layer_extract.json {"format_version", "min_level": level, "motion":
+    when not empty): the header, picture_format.json, display_format.json and layer_hashes.json where present, per GOP
+    exactly layer_file_names(size, level, motion_fill), and layer_extract.json {"format_version", "min_level": level, "motion":
     motion_fill}, which decode_sequence_layer reads.  picture_hashes.json is not copied: the folder cannot produce those
     pictures.  No codec, no GPU.  -> the relative paths written, sorted."""
     import shutil
@@ -386,7 +386,8 @@ def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     _check_against_extract(src_folder, level, motion_fill)
     if os.path.exists(dst_folder) and (not os.path.isdir(dst_folder) or os.listdir(dst_folder)):
         raise ValueError(f"{dst_folder}: not an empty folder; extract_layer writes into a new or empty one")
-    copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, LAYER_HASHES)
+    import pmctf_scale
+    copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, pmctf_scale.DISPLAY_FORMAT, LAYER_HASHES)
               if os.path.exists(os.path.join(src_folder, n))]
     for k, g in enumerate(gops):
         copies += [os.path.join(G.gop_folder(k), n) for n in layer_file_names(g[1], level, motion_fill)]
@@ -417,8 +418,17 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
     that GOP's pictures written.  motion_fill output is never verified, and verify=True is refused with it.
     A folder written by extract_layer (layer_extract.json) refuses a level below its min_level, and motion_fill when it
     holds no motion files for the left-out stages.
+    A folder with a display_format.json has its pictures resampled to the display size after the checks, as
+    decode_sequence_checked does; pmctf_scale.decode_sequence_layer(..., coded_size_output=True) writes them
+    as coded.
     Returns decode_sequence's dict ("frames", "seconds", "verified", "hash_mismatches", "header", "bitdepth") plus "level",
     "times": the source index of every written picture, and "bytes_read": the sizes of the files read, layer_bytes."""
+    return _decode_sequence_layer(codec, bin_folder, yuv_out, level, device, png_out, verify, motion_fill)
+
+
+def _decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False,
+                           coded_size_output=False):
+    """decode_sequence_layer's body; coded_size_output: pmctf_scale.decode_sequence_layer"""
     import contextlib
     import time
     import torch
@@ -453,6 +463,9 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
         layers = read_layer_hashes(bin_folder)
         recorded, hash_level = layers["layers"][str(min(level, top))], layers["level"]
     h, w = header["height"], header["width"]
+    import pmctf_scale
+    display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
+    out_shape = (h, w) if display is None else display.size[::-1]
     q_indexes = G.gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, times = [], [], [], []
     verified = at = nbytes = 0
@@ -474,18 +487,22 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
                 mismatches += bad
                 verified += len(source)
             if f is not None:
-                pictures = G.frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
-                    G.frames_to_u8(out["frames"], h, w)
+                if display is not None:
+                    pictures = display.pictures(out["frames"])
+                else:
+                    pictures = G.frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
+                        G.frames_to_u8(out["frames"], h, w)
                 for planes in pictures:
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:
-                for t, rgb in zip(source, G.frames_to_rgb8(out["frames"], h, w)):
+                rgbs = G.frames_to_rgb8(out["frames"], h, w) if display is None else display.rgb8(out["frames"])
+                for t, rgb in zip(source, rgbs):
                     G.write_pngs(png_out, t, [rgb])
             at += len(source)
             nbytes += out["bytes_read"]
             times += source
-            shapes += [(h, w)] * len(source)
+            shapes += [out_shape] * len(source)
             seconds.append(time.time() - t0)
     return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
             "bitdepth": bitdepth, "level": level, "times": times, "bytes_read": nbytes}

@@ -217,6 +217,17 @@ def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitra
     "bucket_bits", "gops": run_controller's records}; verify_rate_record checks it.
     Returns encode_sequence_gops' dictionary ("gops" with each GOP's "q_index"; the "average ms" lines count accepted
     trials only) plus "rate": run_controller's records, each with "seconds", the wall time of all the GOP's trials."""
+    return _encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device, structure,
+                                 hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
+                                 picture_hash, bitdepth, msssim, q_choices, q_start, bucket_ms, max_trials, slack)
+
+
+def _encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device,
+                          structure="fill", hd_min=None, mad_min=None, ds_factors=(1, 2, 4, 8), skip_decoding=True, psize=128,
+                          src_format="yuv", ingest="host", decoded_frame_path=None, picture_hash=None, bitdepth=8,
+                          msssim=False, q_choices=range(Q_NUM), q_start=None, bucket_ms=1000, max_trials=4, slack=0.0,
+                          scale=None):
+    """encode_sequence_rate with `scale`, a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence_rate)"""
     import shutil
     import pmctf_gop
     import pmctf_seq
@@ -275,7 +286,7 @@ def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitra
                                      structure, pmctf_seq.HD_MIN if hd_min is None else hd_min,
                                      pmctf_seq.MAD_MIN if mad_min is None else mad_min, ds_factors, skip_decoding, psize,
                                      src_format, ingest, decoded_frame_path, picture_hash, bitdepth, msssim,
-                                     what="encode_sequence_rate")
+                                     what="encode_sequence_rate", scale=scale)
     write_rate_record(bin_folder, ctl, [{f: r[f] for f in RECORD_FIELDS} for r in records])
     out["rate"] = records
     return out

@@ -284,15 +284,28 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
                             picture_hash, bitdepth, msssim)
 
 
+def _encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device, structure="fill",
+                          hd_min=HD_MIN, mad_min=MAD_MIN, ds_factors=DS_FACTORS, skip_decoding=True, psize=128,
+                          src_format="yuv", ingest="host", decoded_frame_path=None, picture_hash=None, bitdepth=8,
+                          msssim=False, scale=None):
+    """encode_sequence_gops with `scale`, a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence_gops)"""
+    return _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, None, bin_folder, device, structure,
+                            hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
+                            picture_hash, bitdepth, msssim, scale=scale)
+
+
 def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, choose, bin_folder, device, structure,
                      hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
-                     picture_hash, bitdepth, msssim, what="encode_sequence_gops"):
+                     picture_hash, bitdepth, msssim, what="encode_sequence_gops", scale=None):
     """The body of encode_sequence_gops, shared with pmctf_rate.encode_sequence_rate.  choose is None: every GOP is coded
     once, at q_index, into its folder.  Otherwise q_index is None and choose(k, g, trial) decides GOP k's: trial(q, folder)
     codes the GOP (g: its entry of the list) at q into folder (created) and returns {"q_index", "folder", "bits": 8 x the
     sizes of its files, "seconds", ...}; choose returns the trial it accepts, whose files it has moved to
     bin_folder/gop_{k:05d}.  Only the accepted trial is reconstructed, reported and counted in the "average ms" lines; the
-    GOP entries then carry "q_index" and the header is format version 2."""
+    GOP entries then carry "q_index" and the header is format version 2.
+    scale: a pmctf_scale.CodedSize or None.  With one, every reader resamples its pictures on the device after upload
+    (read_gop_device, whatever `ingest` says; the scene-cut pass too), everything below sees a source of the coded size, the
+    header included, bin_folder gets display_format.json and the result "display_quality"."""
     import io
     import time
     import torch
@@ -331,19 +344,22 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
         plan = _explicit_structure(structure, frame_num, max_gop, psize)
     from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
     from pMCTF.utils.yuv_reader import YUVReader
-    on_device = src_format == "png" or ingest == "device"
+    on_device = src_format == "png" or ingest == "device" or scale is not None
     if on_device or structure == "scenecut":
         G._need_gpu(device, f"{what}(src_format={src_format!r}, ingest={ingest!r}, structure={structure!r})")
 
-    def make_reader():
+    def make_reader(keep=False):
         if src_format == "png":
             reader = G.PNGReader(source)
             if (reader.width, reader.height) != (width, height):
                 raise ValueError(f"the pictures are {reader.width}x{reader.height}, not {width}x{height}")
             if len(reader) < frame_num:
                 raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
-            return reader
-        return YUVReader(source, width, height, start_index=0, bitdepth=bitdepth)
+        else:
+            reader = YUVReader(source, width, height, start_index=0, bitdepth=bitdepth)
+        if scale is not None:
+            reader.resample = scale.ingest(keep)
+        return reader
 
     t0 = time.time()
     extra = {}
@@ -357,7 +373,10 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
         plan = [unit(f, s) for f, s in plan_gops(frame_num, max_gop, extra["cuts"])]
     elif structure == "search":
         extra["searches"] = []
-    reader = make_reader()
+    reader = make_reader(keep=True)
+    display = []
+    if scale is not None:
+        width, height = scale.coded
     read = G.read_gop_device if on_device else G.read_gop
     tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
     lines, ssims, hashes, gops = [], [], [], []
@@ -398,6 +417,8 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
             rec, bits, bits_mv = G.decode_gop(codec, enc["frames_coded"]), enc["bits"], enc["bits_mv"]
         G.report_gop(rec, orig, h, w, bits, bits_mv, g["first"], tables, ssims, hashes, picture_hash=picture_hash,
                      bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
+        if scale is not None:
+            display.extend(scale.display_quality(rec))
         gops.append(dict(g) if choose is None else dict(g, q_index=t["q_index"]))
 
     def code(g, padded, orig, h, w):
@@ -444,6 +465,8 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
         G.write_picture_hashes(bin_folder, picture_hash, hashes)
     if bitdepth > 8:
         G.write_picture_format(bin_folder, bitdepth)
+    if scale is not None:
+        scale.write_header(bin_folder)
     if pairs:
         for key, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
             lines.append(f"{label} {pairs} P frames, average {seconds[key] / pairs * 1000:.0f} ms.")
@@ -456,4 +479,6 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
         out["msssim"] = ssims
     if picture_hash is not None:
         out["picture_hashes"] = hashes
+    if scale is not None:
+        out["display_quality"] = display
     return out

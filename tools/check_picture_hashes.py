@@ -7,7 +7,9 @@ BIN_FOLDER was written by tools/encode_sequence.py --picture-hash u8|f32 (sequen
 --structure, and picture_hashes.json); the
 check is at the u8 level: the CRC-32 of every plane and of every whole frame of DECODED.yuv.  Prints the first mismatching
 frame and plane and exits with status 1 on a mismatch, with status 2 when the folder or the file cannot be checked.
-A folder coded above 8 bits (picture_format.json) is checked at the u16 level: two bytes per sample."""
+A folder coded above 8 bits (picture_format.json) is checked at the u16 level: two bytes per sample.
+A folder coded at another size than its source's (display_format.json) records the hashes of the coded-size pictures:
+DECODED.yuv is then the one tools/decode_sequence.py --coded-size-output writes."""
 import argparse
 import os
 import sys

@@ -17,7 +17,10 @@ depth; the depth found is printed with the summary.
 that level alone: one picture per 2^K of a GOP, a shallower GOP its one low-band picture; the PNGs keep the source
 indices.  Level 1 and above are checked against layer_hashes.json (tools/encode_sequence.py --layer-hashes).
 --motion-fill gives every picture from the same picture files: the motion of the left-out stages is read too and their
-high-band pictures are taken as zero; that output has no hashes to be checked against."""
+high-band pictures are taken as zero; that output has no hashes to be checked against.
+A folder coded with --coded-size (it holds display_format.json) is written at the size of its source: every decoded picture
+is resampled there on the GPU after the hashes, which describe the coded-size pictures, have been checked.
+--coded-size-output writes the pictures as they were coded instead: the file tools/check_picture_hashes.py checks."""
 import argparse
 import json
 import os
@@ -44,6 +47,8 @@ def main():
                     help="decode at 1/2^K of the frame rate from the files of that level alone (default: everything)")
     ap.add_argument("--motion-fill", action="store_true",
                     help="with --temporal-level: full frame rate, the left-out high bands taken as zero (never verified)")
+    ap.add_argument("--coded-size-output", action="store_true",
+                    help="a folder coded with --coded-size: write the coded-size pictures, not the display-size ones")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args()
@@ -56,6 +61,7 @@ def main():
         ap.error("give OUT.yuv, --png DIR or both")
     import torch
     import pmctf_gop
+    import pmctf_scale
     from pMCTF.models.video.pMCTF_L import pMCTF
     header, _ = pmctf_gop.sequence_layout(a.bin_folder)
     net = pMCTF(num_me_stages=header["num_me_stages"]).eval()
@@ -70,16 +76,17 @@ def main():
     with torch.no_grad():
         try:
             if layered:
-                import pmctf_layers
-                out = pmctf_layers.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
-                                                         png_out=a.png, verify=a.verify, motion_fill=a.motion_fill)
+                out = pmctf_scale.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
+                                                        png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
+                                                        coded_size_output=a.coded_size_output)
             else:
-                out = pmctf_gop.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
-                                                        verify=a.verify)
+                out = pmctf_scale.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
+                                                          verify=a.verify, coded_size_output=a.coded_size_output)
         except pmctf_gop.PictureHashMismatch as e:
             sys.exit(f"picture hash mismatch: {e}")
     n = len(out["frames"])
-    print(json.dumps({"frames": n, "height": header["height"], "width": header["width"], "yuv": a.yuv_out, "png": a.png,
+    height, width = out["frames"][0] if n else (header["height"], header["width"])
+    print(json.dumps({"frames": n, "height": height, "width": width, "yuv": a.yuv_out, "png": a.png,
                       "bitdepth": out["bitdepth"],
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
                       "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"]),

@@ -24,7 +24,11 @@ layer, which tools/decode_sequence.py --temporal-level K checks.
 its own, chosen from --q-min..--q-max by coding the GOP up to --max-trials times so that the sequence keeps to the bitrate
 (--bucket-ms: how much unspent rate is carried on; --slack: stop raising q_index within that fraction of the budget;
 --q-index, when given, is where the first GOP starts).  The structure is fill (the default here) or scenecut; search is
-refused.  BIN_FOLDER gets rate_control.json, which tools/check_rate.py checks without a GPU; the choices go to stderr."""
+refused.  BIN_FOLDER gets rate_control.json, which tools/check_rate.py checks without a GPU; the choices go to stderr.
+--coded-size WxH [--chroma-loc center|left] (pmctf_scale): every picture is resampled to W x H on the GPU before it is
+coded (an exact integer Catmull-Rom filter; each side within a factor of 4 of the source's) and everything
+above applies to the resampled sequence.  BIN_FOLDER/display_format.json keeps the source's size, to which
+tools/decode_sequence.py resamples the decoded pictures; the mean PSNR of those against the source goes to stderr."""
 import argparse
 import os
 import sys
@@ -74,9 +78,22 @@ def main(argv=None):
     ap.add_argument("--bitdepth", type=int, default=8, help="bit depth of a .yuv source: 8, or 9..16 for 16-bit samples")
     ap.add_argument("--layer-hashes", action="store_true",
                     help="also record the hashes of the temporal layers (layer_hashes.json), from a full decode of the folder")
+    ap.add_argument("--coded-size", metavar="WxH", help="code at this size instead of the source's (even, within a factor of 4)")
+    ap.add_argument("--chroma-loc", choices=("center", "left"),
+                    help="--coded-size: where the source's chroma samples lie (center: the default; left: MPEG-2 siting)")
     ap.add_argument("source", help=".yuv file or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args(argv)
+    import pmctf_scale
+    coded_size = None
+    if a.coded_size is None:
+        if a.chroma_loc is not None:
+            ap.error("--chroma-loc: only with --coded-size")
+    else:
+        try:
+            coded_size = pmctf_scale.parse_size(a.coded_size)
+        except ValueError as e:
+            ap.error(f"--coded-size: {e}")
     rate_options = {k: getattr(a, k) for k in ("fps", "bucket_ms", "max_trials", "slack", "q_min", "q_max")}
     rate = None
     if a.bitrate is None:
@@ -125,6 +142,11 @@ def main(argv=None):
         src_format, width, height = "yuv", a.width, a.height
         sample_bytes = 2 if a.bitdepth > 8 else 1
         available = os.path.getsize(a.source) // ((width * height + 2 * (width // 2) * (height // 2)) * sample_bytes)
+    if coded_size is not None:
+        try:
+            pmctf_scale.check_sizes(width, height, coded_size[0], coded_size[1], what="--coded-size")
+        except ValueError as e:
+            ap.error(str(e))
     fixed = a.structure == "fixed"
     frames = a.frames if a.frames is not None else (available // a.gop * a.gop if fixed else available)
     if fixed and (frames <= 0 or frames % a.gop or frames > available):
@@ -144,25 +166,25 @@ def main(argv=None):
     net.update(force=True)
     os.makedirs(a.bin_folder, exist_ok=True)
     common = dict(src_format=src_format, decoded_frame_path=a.decoded_frames, msssim=a.msssim, picture_hash=a.picture_hash,
-                  bitdepth=a.bitdepth)
+                  bitdepth=a.bitdepth, coded_size=coded_size, chroma_loc=a.chroma_loc or "center")
     with torch.no_grad():
         if fixed:
-            out = pmctf_gop.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+            out = pmctf_scale.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
                                             keep_gops=True, **common)
         else:
             import pmctf_seq
             cuts = dict(structure=a.structure, hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
                         mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min)
             if rate is not None:
-                out = pmctf_rate.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
+                out = pmctf_scale.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
                                                       a.bin_folder, a.device, **cuts, **common, **rate)
                 for k, r in enumerate(out["rate"]):
                     print(f"GOP {k}: q_index {r['q_index']}, {r['bits']} bits of {r['budget']}"
                           f"{'' if r['fits'] else ' (does not fit)'}, {len(r['trials'])} trial(s), credit {r['credit']}",
                           file=sys.stderr)
             else:
-                out = pmctf_seq.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
-                                                     a.device, **cuts, **common)
+                out = pmctf_scale.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                                                       a.device, **cuts, **common)
             if "cuts" in out:
                 print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
             print("GOPs (first picture: size, motion down-sampling): " +
@@ -175,6 +197,10 @@ def main(argv=None):
             except pmctf_gop.PictureHashMismatch as e:
                 sys.exit(f"picture hash mismatch, no layer hashes written: {e}")
             print(f"layer hashes: {path}", file=sys.stderr)
+    if "display_quality" in out:
+        mean = {k: sum(q[k] for q in out["display_quality"]) / len(out["display_quality"]) for k in out["display_quality"][0]}
+        print(f"coded at {coded_size[0]}x{coded_size[1]}; at {width}x{height} against the source: " +
+              ", ".join(f"{k} {v:.4f}" for k, v in mean.items()), file=sys.stderr)
     print(out["json"])
 
 
