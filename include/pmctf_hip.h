@@ -145,7 +145,9 @@ int pmctf_conv2d_nhwc_geom_opts_f32(const float *x, const float *w_packed, const
 /* Same contract for Cin <= 4 (any Cin >= 1), plain OIHW weights on the device: direct convolution on the vector ALU
  * (first layers: PredictUpdate conv1 1->16 lifting_1d.py:38; PostProcess conv1 1->64 postprocessing.py:35; four-step
  * y_spatial_prior_k.0 1->112 and conv1_context 1|2->112 context_fusion_4step.py:48,63,73,83; masked 1->128
- * context_fusion.py:79; MV encoder first conv 2->64 video_net.py:128). */
+ * context_fusion.py:79; MV encoder first conv 2->64 video_net.py:128).  In this entry point and the two below a tap outside
+ * the image is a zero that is multiplied in (fmaf(+0, w, acc), which turns an accumulator of -0 into +0 for w > 0), as
+ * in the zero-padded copy the specification convolves (tests/valu_conv_census.py, the zero rows). */
 int pmctf_conv2d_smallcin_f32(const float *x, const float *w_oihw, const float *bias,
                               const float *res1, const float *res2, float *y,
                               int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -165,9 +167,17 @@ int pmctf_conv2d_fewcout_f32(const float *x, const float *w_oihw, const float *b
                              const float *res2, float *y, int N, int H, int W, int Cin, int Cout, int K,
                              int act, float slope, int sum_rule, void *stream);
 
-/* depthwise KxK conv, stride 1, pad K/2 (pMCTF/layers/video/layers.py:117-118); x,y [N,H,W,C], w [C,1,K,K] */
+/* depthwise KxK conv, stride 1, pad K/2 (pMCTF/layers/video/layers.py:117-118); x,y [N,H,W,C], w [C,1,K,K].  Here a tap
+ * outside the image is skipped, not multiplied in as a zero: an accumulator of -0 stays -0 beside the border. */
 int pmctf_dwconv2d_nhwc_f32(const float *x, const float *w, const float *bias, float *y,
                             int N, int H, int W, int C, int K, void *stream);
+
+/* Measurement aid (no reference counterpart): which kernel the LAST call of pmctf_conv2d_smallcin_f32,
+ * pmctf_conv3x3_cin1_dual_f32, pmctf_conv2d_fewcout_f32 or pmctf_dwconv2d_nhwc_f32 on the calling thread launched: the
+ * launch expression with its template arguments and the grid, e.g. "conv_smallcin_reg_kernel<3, 2> grid 140"; empty
+ * when that call refused its arguments.  Host text only: no launch, no synchronisation, no allocation.
+ * tests/valu_conv_census.py names the kernel every row must reach. */
+int pmctf_valu_conv_last_launch(char *buf, int capacity);
 
 /* flow_warp / torch_warp (pMCTF/layers/video/video_net.py:32-55): bilinear grid_sample,
  * border padding, align_corners=True.  im,out: [N,C,H,W] planar; flow: [flowN,2,H,W] planar

@@ -11,6 +11,25 @@
 namespace {
 
 inline int launch_ok() { return pm_launch_status(); }
+
+// Measurement aid (pmctf_valu_conv_last_launch): the kernel the LAST convolution entry point of this file called on this
+// host thread launched, as the launch expression with its template arguments, and the grid.  Host text only.
+thread_local char g_valu_last[160];
+inline void clear_valu_launch() { g_valu_last[0] = 0; }
+inline void note_valu_launch(const char *kernel, dim3 g) {
+    int n = 0;
+    while (kernel[n]) ++n;
+    if (n >= 2 && kernel[0] == '(' && kernel[n - 1] == ')') { ++kernel; n -= 2; }      // a templated kernel is parenthesised
+    snprintf(g_valu_last, sizeof(g_valu_last), "%.*s grid %u", n, kernel, g.x);
+}
+// PM_LAUNCH that also notes what it launches (a macro argument is expanded before it is stringified here, so the
+// PM_STRIP / PM_SC / PM_FC call sites note their template arguments as numbers)
+#define PM_LAUNCH_NOTED(kernel, grid, ...)        \
+    do {                                          \
+        note_valu_launch(#kernel, grid);          \
+        PM_LAUNCH(kernel, grid, __VA_ARGS__);     \
+    } while (0)
+
 inline unsigned nblocks(long n, int bs = 256) {
     long b = (n + bs - 1) / bs;
     return (unsigned)(b < 1 ? 1 : b);
@@ -19,6 +38,8 @@ inline unsigned nblocks(long n, int bs = 256) {
 // ---------------------------------------------------------------------------------
 // direct conv for Cin <= 4: one thread per output element, cout fastest (NHWC store).
 // acc = bias; for ky: for kx: for ci: fmaf   (single 16-channel chunk of the spec order)
+// A tap outside the image is a zero that is MULTIPLIED IN, as in the padded copy of oracle/c/pm_ops.c: skipping it is
+// another value when the accumulator is -0 (fmaf(+0, w, -0) is +0 for w > 0), and quantised subbands are full of -0.
 __global__ void conv_smallcin_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                      const float *__restrict__ bias, const float *res1, const float *res2,
                                      float *y, int N, int H, int W, int Cin, int Cout, int KH, int KW, int S,
@@ -63,24 +84,23 @@ __global__ void conv_smallcin_kernel(const float *__restrict__ x, const float *_
             for (int ci = 0; ci < Cin; ++ci)
                 for (int ky = 0; ky < KH; ++ky) {
                     const int iy = oy * S + ky - ph;
-                    if (iy < 0 || iy >= H) continue;
+                    const bool rowok = iy >= 0 && iy < H;
                     for (int kx = 0; kx < KW; ++kx) {
                         const int ix = ox * S + kx - pw;
-                        if (ix < 0 || ix >= W) continue;
-                        acc = __builtin_fmaf(x[(((long)n * H + iy) * W + ix) * Cin + ci],
-                                             wl[((ky * KW + kx) * Cin + ci) * Cout + co], acc);
+                        const float v = (rowok && ix >= 0 && ix < W) ? x[(((long)n * H + iy) * W + ix) * Cin + ci] : 0.0f;
+                        acc = __builtin_fmaf(v, wl[((ky * KW + kx) * Cin + ci) * Cout + co], acc);
                     }
                 }
         } else {
             for (int ky = 0; ky < KH; ++ky) {
                 const int iy = oy * S + ky - ph;
-                if (iy < 0 || iy >= H) continue;
+                const bool rowok = iy >= 0 && iy < H;
                 for (int kx = 0; kx < KW; ++kx) {
                     const int ix = ox * S + kx - pw;
-                    if (ix < 0 || ix >= W) continue;
-                    const float *xp = x + (((long)n * H + iy) * W + ix) * Cin;
+                    const bool ok = rowok && ix >= 0 && ix < W;
+                    const float *xp = x + (ok ? (((long)n * H + iy) * W + ix) * Cin : 0L);
                     const float *wp = wl + ((ky * KW + kx) * Cin) * Cout + co;
-                    for (int ci = 0; ci < Cin; ++ci) acc = __builtin_fmaf(xp[ci], wp[ci * Cout], acc);
+                    for (int ci = 0; ci < Cin; ++ci) acc = __builtin_fmaf(ok ? xp[ci] : 0.0f, wp[ci * Cout], acc);
                 }
             }
         }
@@ -96,7 +116,8 @@ __global__ void conv_smallcin_kernel(const float *__restrict__ x, const float *_
 // Specialised direct conv for the small-Cin layers that dominate this family (3x3 with 1..3 input channels, 1x1 with 2):
 // a thread owns ONE output channel (its K*K*CIN weights + bias live in registers) and walks over pixels; the
 // 256-thread block covers PPP = 256/Cout pixels per pass, stores are contiguous over cout, the input taps of a pixel
-// are wave-broadcast loads.  Same sum order as the generic kernel: acc = bias; for ky: for kx: for ci: fmaf.
+// are wave-broadcast loads.  Same sum order as the generic kernel: acc = bias; for ky: for kx: for ci: fmaf, a tap
+// outside the image multiplied in as a zero.
 template <int K, int CIN>
 __global__ void conv_smallcin_reg_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                          const float *__restrict__ bias, const float *res1, const float *res2, float *y,
@@ -125,11 +146,11 @@ __global__ void conv_smallcin_reg_kernel(const float *__restrict__ x, const floa
 #pragma unroll
             for (int kx = 0; kx < K; ++kx) {
                 const int ix = ox * S + kx - pw;
-                if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-                    const float *xp = x + ((size_t)(n * H + iy) * W + ix) * CIN;
+                const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
+                const float *xp = x + (ok ? ((size_t)(n * H + iy) * W + ix) * CIN : (size_t)0);
 #pragma unroll
-                    for (int ci = 0; ci < CIN; ++ci) acc = __builtin_fmaf(xp[ci], wr[(ky * K + kx) * CIN + ci], acc);
-                }
+                for (int ci = 0; ci < CIN; ++ci)
+                    acc = __builtin_fmaf(ok ? xp[ci] : 0.0f, wr[(ky * K + kx) * CIN + ci], acc);
             }
         }
         if (rule) acc = acc + b;
@@ -448,7 +469,10 @@ __global__ void dwconv_kernel(const float *__restrict__ x, const float *__restri
 
 // depthwise 3x3 for C % 4 == 0: a thread owns 4 consecutive channels of a strip of PX consecutive pixels, keeps its
 // 36 weights in registers, reads the 3 x (PX+2) input window once as 16-byte loads and writes PX 16-byte stores.
-// Same sum order as dwconv_kernel: acc = bias; for ky: for kx: fmaf.
+// Same sum order as dwconv_kernel: acc = bias; for ky: for kx: fmaf, and like it (and pm_dwconv2d of the oracle) a tap
+// outside the image is SKIPPED, not multiplied in as a zero: fmaf(+0, w, -0) is +0 for w > 0, the skipped tap leaves -0.
+// Of the window's PX + 2 columns only the first can lie left of the image and only a tap right of its own pixel
+// (kx = 2) right of it, for a pixel that is stored: the other taps need no test.
 template <int PX>
 __global__ __launch_bounds__(256) void dwconv3_strip_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                             const float *__restrict__ bias, float *y, int N, int H, int W,
@@ -474,19 +498,21 @@ __global__ __launch_bounds__(256) void dwconv3_strip_kernel(const float *__restr
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int iy = oy + ky - 1;
-            const bool rowok = iy >= 0 && iy < H;
-            const float *row = x + ((n * H + (rowok ? iy : 0)) * W) * C + c;
+            if (iy < 0 || iy >= H) continue;
+            const float *row = x + ((n * H + iy) * W) * C + c;
             float4 in[PX + 2];
 #pragma unroll
             for (int j = 0; j < PX + 2; ++j) {
                 const int ix = sx + j - 1;
-                in[j] = (rowok && ix >= 0 && ix < W) ? *(const float4 *)(row + (long)ix * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+                in[j] = (ix >= 0 && ix < W) ? *(const float4 *)(row + (long)ix * C) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const float4 wt = wr[ky * 3 + kx];
 #pragma unroll
                 for (int j = 0; j < PX; ++j) {
+                    const int ix = sx + j + kx - 1;
+                    if ((kx == 0 && j == 0 && ix < 0) || (kx == 2 && ix >= W)) continue;
                     acc[j].x = __builtin_fmaf(in[j + kx].x, wt.x, acc[j].x);
                     acc[j].y = __builtin_fmaf(in[j + kx].y, wt.y, acc[j].y);
                     acc[j].z = __builtin_fmaf(in[j + kx].z, wt.z, acc[j].z);
@@ -503,7 +529,8 @@ __global__ __launch_bounds__(256) void dwconv3_strip_kernel(const float *__restr
 
 // The same with a vertical walk: a thread owns 4 channels of a PX-wide column of RY output rows and keeps a rolling window
 // of three input rows in registers, so every input row is loaded once per thread instead of three times ((RY+2)/RY x
-// (PX+2)/PX = 1.9x read amplification through L1 instead of 4.5x).  Same fmaf chain per output: acc = bias; ky, kx.
+// (PX+2)/PX = 1.9x read amplification through L1 instead of 4.5x).  Same fmaf chain per output: acc = bias; ky, kx, the
+// taps outside the image skipped as in the strip kernel.
 template <int PX, int RY>
 __global__ __launch_bounds__(256) void dwconv3_column_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                              const float *__restrict__ bias, float *y, int N, int H, int W,
@@ -546,12 +573,16 @@ __global__ __launch_bounds__(256) void dwconv3_column_kernel(const float *__rest
             for (int j = 0; j < PX; ++j) acc[j] = b;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
+                const int iy = oy + ky - 1;
+                if (iy < 0 || iy >= H) continue;
                 const float4 *in = win[(ry + ky) % 3];
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
                     const float4 wt = wr[ky * 3 + kx];
 #pragma unroll
                     for (int j = 0; j < PX; ++j) {
+                        const int ix = sx + j + kx - 1;
+                        if ((kx == 0 && j == 0 && ix < 0) || (kx == 2 && ix >= W)) continue;
                         acc[j].x = __builtin_fmaf(in[j + kx].x, wt.x, acc[j].x);
                         acc[j].y = __builtin_fmaf(in[j + kx].y, wt.y, acc[j].y);
                         acc[j].z = __builtin_fmaf(in[j + kx].z, wt.z, acc[j].z);
@@ -684,6 +715,7 @@ extern "C" int pmctf_conv2d_smallcin_f32(const float *x, const float *w, const f
                                          const float *res2, float *y, int N, int H, int W, int Cin, int Cout,
                                          int KH, int KW, int stride, int pad_h, int pad_w, int act, float slope,
                                          int sum_rule, void *stream) {
+    clear_valu_launch();
     if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin > 4 || Cout <= 0 || KH <= 0 || KW <= 0 ||
         stride <= 0 || (sum_rule != PMCTF_SUM_CHAIN && sum_rule != PMCTF_SUM_BLOCKS && sum_rule != PMCTF_SUM_GEMM &&
                         sum_rule != PMCTF_SUM_GEMV_3X3) ||
@@ -703,8 +735,8 @@ extern "C" int pmctf_conv2d_smallcin_f32(const float *x, const float *w, const f
         dim3 grid((unsigned)nb), block(256);
         hipStream_t st = (hipStream_t)stream;
 #define PM_STRIP(C_)                                                                                                 \
-    PM_LAUNCH((conv3x3_smallcin_strip_kernel<C_>), grid, block, 0, st, x, w, bias, res1, res2, y, N, H, W, Cout, act,  \
-              slope, Q, G, wstrips_per_row, total_items, rule);                                                      \
+    PM_LAUNCH_NOTED((conv3x3_smallcin_strip_kernel<C_>), grid, block, 0, st, x, w, bias, res1, res2, y, N, H, W, Cout,  \
+                    act, slope, Q, G, wstrips_per_row, total_items, rule);                                           \
     return launch_ok();
         if (Cin == 1) { PM_STRIP(1) }
         if (Cin == 2) { PM_STRIP(2) }
@@ -718,8 +750,8 @@ extern "C" int pmctf_conv2d_smallcin_f32(const float *x, const float *w, const f
         dim3 grid((unsigned)nb), block(256);
         hipStream_t st = (hipStream_t)stream;
 #define PM_SC(K_, C_)                                                                                               \
-    PM_LAUNCH((conv_smallcin_reg_kernel<K_, C_>), grid, block, 0, st, x, w, bias, res1, res2, y, N, H, W, Cout, stride,  \
-              pad_h, pad_w, Ho, Wo, act, slope, rule);                                                              \
+    PM_LAUNCH_NOTED((conv_smallcin_reg_kernel<K_, C_>), grid, block, 0, st, x, w, bias, res1, res2, y, N, H, W, Cout,  \
+                    stride, pad_h, pad_w, Ho, Wo, act, slope, rule);                                                \
     return launch_ok();
         if (KH == 3 && Cin == 1) { PM_SC(3, 1) }
         if (KH == 3 && Cin == 2) { PM_SC(3, 2) }
@@ -732,18 +764,19 @@ extern "C" int pmctf_conv2d_smallcin_f32(const float *x, const float *w, const f
     const long total = (long)N * Ho * Wo * Cout;
     unsigned g = nblocks(total);
     if (g > 8192) g = 8192;
-    PM_LAUNCH(conv_smallcin_kernel, dim3(g), dim3(256), smem, (hipStream_t)stream, x, w, bias, res1, res2, y,
+    PM_LAUNCH_NOTED(conv_smallcin_kernel, dim3(g), dim3(256), smem, (hipStream_t)stream, x, w, bias, res1, res2, y,
                        N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, Ho, Wo, act, slope, rule);
     return launch_ok();
 }
 
 extern "C" int pmctf_conv3x3_cin1_dual_f32(const float *x, const float *w, const float *bias, float *y, float *y2, int N,
                                            int H, int W, int Cout, int act2, float slope, int sum_rule, void *stream) {
+    clear_valu_launch();
     if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || Cout != 16 || (sum_rule != 0 && sum_rule != 1)) return PMCTF_EINVAL;
     unsigned g = nblocks((long)N * H * W);
     if (g > 16384) g = 16384;
-    PM_LAUNCH(conv3x3_cin1_pix16_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, y2, N, H, W, act2,
-              slope, sum_rule);
+    PM_LAUNCH_NOTED(conv3x3_cin1_pix16_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, y2, N, H, W,
+                    act2, slope, sum_rule);
     return launch_ok();
 }
 
@@ -754,6 +787,7 @@ extern "C" int pmctf_conv2d_fewcout_supported(int Cin, int Cout, int K) {
 extern "C" int pmctf_conv2d_fewcout_f32(const float *x, const float *w, const float *bias, const float *res1,
                                         const float *res2, float *y, int N, int H, int W, int Cin, int Cout, int K,
                                         int act, float slope, int sum_rule, void *stream) {
+    clear_valu_launch();
     if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || !pmctf_conv2d_fewcout_supported(Cin, Cout, K) ||
         (sum_rule != 0 && sum_rule != 1))
         return PMCTF_EINVAL;
@@ -766,12 +800,12 @@ extern "C" int pmctf_conv2d_fewcout_f32(const float *x, const float *w, const fl
 #define PM_FC(K_, CI_, CO_)                                                                                           \
     if (use_lds && tiles <= 0x7fffffffL && (long)H * W * CI_ < 0x7fffffffL) {                                         \
         const size_t smem = (size_t)(8 + K_ - 1) * (32 + K_ - 1) * 20 * sizeof(float);                                \
-        PM_LAUNCH((conv_fewcout_lds_kernel<K_, CI_, CO_>), dim3((unsigned)tiles), dim3(256), smem, st, x, w, bias,     \
-                  res1, res2, y, H, W, tiles_x, tiles_y, act, slope, sum_rule);                                       \
+        PM_LAUNCH_NOTED((conv_fewcout_lds_kernel<K_, CI_, CO_>), dim3((unsigned)tiles), dim3(256), smem, st, x, w,    \
+                        bias, res1, res2, y, H, W, tiles_x, tiles_y, act, slope, sum_rule);                           \
         return launch_ok();                                                                                           \
     }                                                                                                                 \
-    PM_LAUNCH((conv_fewcout_pix_kernel<K_, CI_, CO_>), dim3(g), dim3(256), 0, st, x, w, bias, res1, res2, y, N, H, W,   \
-              act, slope, sum_rule);                                                                                  \
+    PM_LAUNCH_NOTED((conv_fewcout_pix_kernel<K_, CI_, CO_>), dim3(g), dim3(256), 0, st, x, w, bias, res1, res2, y, N, \
+                    H, W, act, slope, sum_rule);                                                                      \
     return launch_ok();
     if (K == 3 && Cin == 16) { PM_FC(3, 16, 1) }
     if (K == 3 && Cin == 64) { PM_FC(3, 64, 1) }
@@ -781,6 +815,7 @@ extern "C" int pmctf_conv2d_fewcout_f32(const float *x, const float *w, const fl
 
 extern "C" int pmctf_dwconv2d_nhwc_f32(const float *x, const float *w, const float *bias, float *y, int N, int H,
                                        int W, int C, int K, void *stream) {
+    clear_valu_launch();
     if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || !(K & 1)) return PMCTF_EINVAL;
     if (K == 3 && (C & 3) == 0) {
         static const int column = [] { const char *e = getenv("PMCTF_DWCONV_COLUMN"); return e ? atoi(e) : 1; }();
@@ -788,18 +823,25 @@ extern "C" int pmctf_dwconv2d_nhwc_f32(const float *x, const float *w, const flo
         if (column && threads_col >= 256L * 1024) {          // enough columns to fill the chip four times over
             unsigned gc = nblocks(threads_col);
             if (gc > 16384) gc = 16384;
-            PM_LAUNCH((dwconv3_column_kernel<4, 8>), dim3(gc), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H, W, C);
+            PM_LAUNCH_NOTED((dwconv3_column_kernel<4, 8>), dim3(gc), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H,
+                            W, C);
             return launch_ok();
         }
         unsigned g4 = nblocks((long)N * H * ((W + 3) / 4) * (C / 4));
         if (g4 > 16384) g4 = 16384;
-        PM_LAUNCH(dwconv3_strip_kernel<4>, dim3(g4), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H, W, C);
+        PM_LAUNCH_NOTED(dwconv3_strip_kernel<4>, dim3(g4), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H, W, C);
         return launch_ok();
     }
     unsigned g = nblocks((long)N * H * W * C);
     if (g > 16384) g = 16384;
-    PM_LAUNCH(dwconv_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H, W, C, K);
+    PM_LAUNCH_NOTED(dwconv_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, N, H, W, C, K);
     return launch_ok();
+}
+
+extern "C" int pmctf_valu_conv_last_launch(char *buf, int capacity) {
+    if (!buf || capacity <= 0) return PMCTF_EINVAL;
+    snprintf(buf, (size_t)capacity, "%s", g_valu_last);
+    return PMCTF_OK;
 }
 
 extern "C" int pmctf_flow_warp_f32(const float *im, const float *flow, const float *lin_x, const float *lin_y,

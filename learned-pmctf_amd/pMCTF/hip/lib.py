@@ -37,6 +37,7 @@ _SIGS = {
     "pmctf_mv_fourpart_estimate_f32": (ci, [vp] * 4 + [ci] * 3 + [vp, vp]),
     "pmctf_sqdiff_sum_f32": (ci, [vp, vp, i64, vp, vp]),
     "pmctf_dwconv2d_nhwc_f32": (ci, [vp] * 4 + [ci] * 5 + [vp]),
+    "pmctf_valu_conv_last_launch": (ci, [C.c_char_p, ci]),                        # measurement aid
     "pmctf_flow_warp_f32": (ci, [vp] * 5 + [ci] * 5 + [cf, vp]),
     "pmctf_avgpool2_f32": (ci, [vp, vp, ci, ci, ci, vp]),
     "pmctf_bilinear_up2_f32": (ci, [vp, vp, ci, ci, ci, cf, vp]),

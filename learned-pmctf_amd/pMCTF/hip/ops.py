@@ -178,12 +178,13 @@ class Conv2d:
         return y
 
 
-def conv3x3_cin1_dual(conv, x, act2):
+def conv3x3_cin1_dual(conv, x, act2, out=None, out2=None):
     """conv: a 1->16 3x3 'same' Conv2d; x (N,H,W,1).  Returns (conv(x), act2(conv(x))) from one launch."""
     assert conv.small and conv.Cin == 1 and conv.Cout == 16 and conv.KH == 3 and conv.stride == 1 and conv.pad == (1, 1)
     N, H, W, _ = x.shape
-    y = torch.empty((N, H, W, 16), dtype=torch.float32, device=x.device)
-    y2 = torch.empty_like(y)
+    y = out if out is not None else torch.empty((N, H, W, 16), dtype=torch.float32, device=x.device)
+    y2 = out2 if out2 is not None else torch.empty_like(y)
+    assert tuple(y.shape) == tuple(y2.shape) == (N, H, W, 16)
     _lib.check(_lib.hip().pmctf_conv3x3_cin1_dual_f32(_p(x), _p(conv.w), _p(conv.b), _p(y), _p(y2), N, H, W, 16, int(act2),
                                                       0.0, conv.rule, _stream()), "conv3x3_cin1_dual")
     return y, y2
@@ -195,13 +196,22 @@ class DepthwiseConv2d:
         self.w = weight.detach().to(device, torch.float32).contiguous()
         self.b = None if bias is None else bias.detach().to(device, torch.float32).contiguous()
 
-    def __call__(self, x):
+    def __call__(self, x, out=None):
         N, H, W, Cc = x.shape
         assert Cc == self.C
-        y = torch.empty_like(x)
+        y = out if out is not None else torch.empty_like(x)
+        assert tuple(y.shape) == tuple(x.shape)
         _lib.check(_lib.hip().pmctf_dwconv2d_nhwc_f32(_p(x), _p(self.w), _p(self.b), _p(y), N, H, W, Cc, self.K,
                                                       _stream()), "dwconv2d")
         return y
+
+
+def valu_conv_last_launch():
+    """Measurement aid: 'kernel expression grid G' of the last small-Cin / cin1-dual / few-cout / depthwise convolution
+    this thread launched (csrc/basic_ops.hip), '' when that call refused its arguments"""
+    buf = C.create_string_buffer(160)
+    _lib.check(_lib.hip().pmctf_valu_conv_last_launch(buf, 160), "valu_conv_last_launch")
+    return buf.value.decode()
 
 
 def flow_warp(im, flow, lin_x, lin_y, sign=1.0):

@@ -225,8 +225,9 @@ void pm_conv2d_rule(const float *restrict x, const float *restrict w, const floa
                     int stride, int pad_h, int pad_w, int rule) {
     const int Ho = (H + 2 * pad_h - KH) / stride + 1;
     const int Wo = (W + 2 * pad_w - KW) / stride + 1;
-    /* zero-padded copy of the input: out-of-image taps then contribute fmaf(0, w, acc) == acc,
-     * which is the same value as skipping them */
+    /* zero-padded copy of the input: out-of-image taps contribute fmaf(+0, w, acc).  That is acc for every acc but -0
+     * (fmaf(+0, w, -0) is +0 for w > 0), so it is NOT the same as skipping them: the zeros are part of this convolution's
+     * definition, and a kernel held to it multiplies them in (pm_dwconv2d below skips them, and so do its kernels) */
     const int Wo_pad = (Wo + PM_XB - 1) / PM_XB * PM_XB;
     const int Hp = (Ho - 1) * stride + KH;
     const int Wp = (Wo_pad - 1) * stride + KW;
