@@ -186,7 +186,7 @@ int pmctf_valu_conv_last_launch(char *buf, int capacity);
 int pmctf_flow_warp_f32(const float *im, const float *flow, const float *lin_x, const float *lin_y,
                         float *out, int N, int C, int H, int W, int flowN, float flow_sign, void *stream);
 
-/* F.avg_pool2d(k=2,s=2) on NC planes (video_net.py:106-108) */
+/* F.avg_pool2d(k=2,s=2) on NC planes (video_net.py:106-108): 0 + ((((0 + a00) + a01) + a10) + a11) / 4, never -0 */
 int pmctf_avgpool2_f32(const float *x, float *y, int NC, int H, int W, void *stream);
 /* F.interpolate bilinear x2, align_corners=False, result times `scale` (video_net.py:58-63,114) */
 int pmctf_bilinear_up2_f32(const float *x, float *y, int NC, int H, int W, float scale, void *stream);
@@ -224,6 +224,12 @@ int pmctf_bilinear_down_f32(const float *x, float *y, int NC, int H, int W, int 
 #define PMCTF_EW_LAST 17
 int pmctf_ew_f32(int op, float *out, const int64_t *so, const float *a, const int64_t *sa, const float *b,
                  const int64_t *sb, int N, int C, int H, int W, float alpha, float beta, int cfast, void *stream);
+/* Measurement aid: the kernel the last call of pmctf_ew_f32, pmctf_nearest_up2_nhwc_f32 or pmctf_pixel_shuffle2_nhwc_f32 on
+ * the calling thread launched, as the launch expression with its template arguments, " channels" or " rows" for the two
+ * forms of ew_c4_kernel, and the grid, e.g. "ew_c4_kernel<int> rows grid 3"; empty when that call refused its arguments.
+ * Host text only: no launch, no synchronisation, no allocation.  tests/ew_census.py names the kernel every row must
+ * reach. */
+int pmctf_ew_last_launch(char *buf, int capacity);
 
 /* SpyNet level input torch.cat([im1, warp(im2), flow_up]) (video_net.py:116-119) for Y-only frames
  * (3 identical channels, pMCTF_L.py:453-454): planes im1[HW], warped[HW], flow_up[2][HW] -> NHWC [HW,8]. */

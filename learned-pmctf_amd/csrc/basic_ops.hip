@@ -650,10 +650,11 @@ __global__ void avgpool2_kernel(const float *__restrict__ x, float *y, int NC, i
         const long nc = pm_div(p, Ho);
         const float *r0 = x + (nc * H + 2 * oy) * W + 2 * ox;
         const float *r1 = r0 + W;
-        float s = r0[0] + r0[1];
+        float s = 0.0f + r0[0];       // ATen's sum starts at +0 and its quotient is ADDED to a zeroed output: no result
+        s = s + r0[1];                // is -0, neither from a window of four -0 nor from a negative quotient that underflows
         s = s + r1[0];
         s = s + r1[1];
-        y[idx] = s / 4.0f;
+        y[idx] = 0.0f + s / 4.0f;
     }
 }
 

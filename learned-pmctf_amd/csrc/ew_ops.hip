@@ -16,6 +16,23 @@ inline unsigned grid_for(long n, int bs = 256, unsigned cap = 16384) {
     return (unsigned)(b > cap ? cap : b);
 }
 
+// Measurement aid (pmctf_ew_last_launch): the kernel the LAST call of pmctf_ew_f32, pmctf_nearest_up2_nhwc_f32 or
+// pmctf_pixel_shuffle2_nhwc_f32 on this host thread launched, as the launch expression with its template arguments, the
+// form where one instantiation serves two (ew_c4_kernel: channels / rows), and the grid.  Host text only.
+thread_local char g_ew_last[160];
+inline void clear_ew_launch() { g_ew_last[0] = 0; }
+inline void note_ew_launch(const char *kernel, const char *form, dim3 g) {
+    int n = 0;
+    while (kernel[n]) ++n;
+    if (n >= 2 && kernel[0] == '(' && kernel[n - 1] == ')') { ++kernel; n -= 2; }      // a templated kernel is parenthesised
+    snprintf(g_ew_last, sizeof(g_ew_last), "%.*s%s grid %u", n, kernel, form, g.x);
+}
+#define PM_LAUNCH_NOTED(kernel, form, grid, ...)  \
+    do {                                          \
+        note_ew_launch(#kernel, form, grid);      \
+        PM_LAUNCH(kernel, grid, __VA_ARGS__);     \
+    } while (0)
+
 struct View { long s[4]; };  // element strides of the logical (n,c,h,w) index
 
 __device__ __forceinline__ float ew_apply(int op, float a, float b, float alpha, float beta) {
@@ -449,6 +466,7 @@ __global__ void mv_dequant_kernel(const float *__restrict__ so_far, const float 
 extern "C" int pmctf_ew_f32(int op, float *out, const int64_t *so, const float *a, const int64_t *sa, const float *b,
                             const int64_t *sb, int N, int C, int H, int W, float alpha, float beta, int cfast,
                             void *stream) {
+    clear_ew_launch();
     if (!out || !a || !so || !sa || N <= 0 || C <= 0 || H <= 0 || W <= 0 || op < 0 || op > PMCTF_EW_LAST)
         return PMCTF_EINVAL;
     View vo, va, vb;
@@ -463,16 +481,16 @@ extern "C" int pmctf_ew_f32(int op, float *out, const int64_t *so, const float *
         if (same && dense_strides(vo.s, d)) {
             const bool vec = (total & 3) == 0 && (((uintptr_t)out | (uintptr_t)a | (uintptr_t)b) & 15) == 0;
             if (vec)
-                PM_LAUNCH(ew_flat_kernel<true>, dim3(grid_for(total >> 2)), dim3(256), 0, st, op, out, a, b, total, alpha, beta);
+                PM_LAUNCH_NOTED(ew_flat_kernel<true>, "", dim3(grid_for(total >> 2)), dim3(256), 0, st, op, out, a, b, total, alpha, beta);
             else
-                PM_LAUNCH(ew_flat_kernel<false>, dim3(grid_for(total)), dim3(256), 0, st, op, out, a, b, total, alpha, beta);
+                PM_LAUNCH_NOTED(ew_flat_kernel<false>, "", dim3(grid_for(total)), dim3(256), 0, st, op, out, a, b, total, alpha, beta);
             return launch_ok();
         }
     }
     if (!b && H > 1 && W > 1 && vo.s[3] == 1 && vo.s[2] == W && va.s[2] == 1 && va.s[3] == H && (long)N * C < 65536 &&
         (N == 1 || (vo.s[0] >= (long)H * W && va.s[0] >= (long)H * W)) && (C == 1 || (vo.s[1] >= (long)H * W && va.s[1] >= (long)H * W))) {
         const dim3 grid((unsigned)((W + 31) / 32), (unsigned)((H + 31) / 32), (unsigned)(N * C));
-        PM_LAUNCH(ew_transpose_kernel, grid, dim3(256), 0, st, op, out, a, C, H, W, vo.s[0], vo.s[1], va.s[0], va.s[1], alpha, beta);
+        PM_LAUNCH_NOTED(ew_transpose_kernel, "", grid, dim3(256), 0, st, op, out, a, C, H, W, vo.s[0], vo.s[1], va.s[0], va.s[1], alpha, beta);
         return launch_ok();
     }
     const bool small = total < (1L << 31);
@@ -484,8 +502,8 @@ extern "C" int pmctf_ew_f32(int op, float *out, const int64_t *so, const float *
             if (i != 1 && dims[i] != 1 && (((vo.s[i] | va.s[i]) & 3) != 0 || (b && (vb.s[i] & 3) != 0))) ok4 = false;
         if (ok4) {
             const unsigned g = grid_for(total >> 2);
-            if (small) PM_LAUNCH((ew_c4_kernel<int>), dim3(g), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C / 4, H, W, alpha, beta);
-            else PM_LAUNCH((ew_c4_kernel<long>), dim3(g), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C / 4, H, W, alpha, beta);
+            if (small) PM_LAUNCH_NOTED((ew_c4_kernel<int>), " channels", dim3(g), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C / 4, H, W, alpha, beta);
+            else PM_LAUNCH_NOTED((ew_c4_kernel<long>), " channels", dim3(g), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C / 4, H, W, alpha, beta);
             return launch_ok();
         }
     }
@@ -500,19 +518,25 @@ extern "C" int pmctf_ew_f32(int op, float *out, const int64_t *so, const float *
         if (ok4) {
             auto rows = [](const View &v) { View r; r.s[0] = v.s[0]; r.s[1] = 1; r.s[2] = v.s[1]; r.s[3] = v.s[2]; return r; };
             const unsigned g = grid_for(total >> 2);
-            if (small) PM_LAUNCH((ew_c4_kernel<int>), dim3(g), dim3(256), 0, st, op, out, rows(vo), a, rows(va), b, rows(vb), N, W / 4, C, H, alpha, beta);
-            else PM_LAUNCH((ew_c4_kernel<long>), dim3(g), dim3(256), 0, st, op, out, rows(vo), a, rows(va), b, rows(vb), N, W / 4, C, H, alpha, beta);
+            if (small) PM_LAUNCH_NOTED((ew_c4_kernel<int>), " rows", dim3(g), dim3(256), 0, st, op, out, rows(vo), a, rows(va), b, rows(vb), N, W / 4, C, H, alpha, beta);
+            else PM_LAUNCH_NOTED((ew_c4_kernel<long>), " rows", dim3(g), dim3(256), 0, st, op, out, rows(vo), a, rows(va), b, rows(vb), N, W / 4, C, H, alpha, beta);
             return launch_ok();
         }
     }
     if (cfast) {
-        if (small) PM_LAUNCH((ew_kernel<true, int>), dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
-        else PM_LAUNCH((ew_kernel<true, long>), dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
+        if (small) PM_LAUNCH_NOTED((ew_kernel<true, int>), "", dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
+        else PM_LAUNCH_NOTED((ew_kernel<true, long>), "", dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
     } else {
-        if (small) PM_LAUNCH((ew_kernel<false, int>), dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
-        else PM_LAUNCH((ew_kernel<false, long>), dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
+        if (small) PM_LAUNCH_NOTED((ew_kernel<false, int>), "", dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
+        else PM_LAUNCH_NOTED((ew_kernel<false, long>), "", dim3(grid_for(total)), dim3(256), 0, st, op, out, vo, a, va, b, vb, N, C, H, W, alpha, beta);
     }
     return launch_ok();
+}
+
+extern "C" int pmctf_ew_last_launch(char *buf, int capacity) {
+    if (!buf || capacity <= 0) return PMCTF_EINVAL;
+    snprintf(buf, (size_t)capacity, "%s", g_ew_last);
+    return PMCTF_OK;
 }
 
 extern "C" int pmctf_spynet_pack8_f32(const float *im1, const float *warped, const float *flow_up, float *out, int H,
@@ -532,26 +556,28 @@ extern "C" int pmctf_lift_skip3_f32(const float *x, float *y, int NC, int H, int
 }
 
 extern "C" int pmctf_nearest_up2_nhwc_f32(const float *x, float *y, int N, int H, int W, int C, void *stream) {
+    clear_ew_launch();
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return PMCTF_EINVAL;
     if ((C & 3) == 0) {
-        PM_LAUNCH(nearest_up2_vec4_kernel, dim3(grid_for((long)N * H * W * (C >> 2))), dim3(256), 0, (hipStream_t)stream, x,
+        PM_LAUNCH_NOTED(nearest_up2_vec4_kernel, "", dim3(grid_for((long)N * H * W * (C >> 2))), dim3(256), 0, (hipStream_t)stream, x,
                   y, N, H, W, C);
         return launch_ok();
     }
-    PM_LAUNCH(nearest_up2_kernel, dim3(grid_for((long)N * H * W * C * 4)), dim3(256), 0, (hipStream_t)stream, x,
+    PM_LAUNCH_NOTED(nearest_up2_kernel, "", dim3(grid_for((long)N * H * W * C * 4)), dim3(256), 0, (hipStream_t)stream, x,
                        y, N, H, W, C);
     return launch_ok();
 }
 
 extern "C" int pmctf_pixel_shuffle2_nhwc_f32(const float *x, float *y, int N, int H, int W, int C, int act, float slope,
                                              void *stream) {
+    clear_ew_launch();
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return PMCTF_EINVAL;
     if ((C & 3) == 0) {
-        PM_LAUNCH(pixel_shuffle2_vec4_kernel, dim3(grid_for((long)N * H * W * (C >> 2))), dim3(256), 0, (hipStream_t)stream,
+        PM_LAUNCH_NOTED(pixel_shuffle2_vec4_kernel, "", dim3(grid_for((long)N * H * W * (C >> 2))), dim3(256), 0, (hipStream_t)stream,
                   x, y, N, H, W, C, act, slope);
         return launch_ok();
     }
-    PM_LAUNCH(pixel_shuffle2_kernel, dim3(grid_for((long)N * H * W * C * 4)), dim3(256), 0, (hipStream_t)stream,
+    PM_LAUNCH_NOTED(pixel_shuffle2_kernel, "", dim3(grid_for((long)N * H * W * C * 4)), dim3(256), 0, (hipStream_t)stream,
                        x, y, N, H, W, C, act, slope);
     return launch_ok();
 }

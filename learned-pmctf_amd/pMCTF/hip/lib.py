@@ -45,6 +45,7 @@ _SIGS = {
     "pmctf_bilinear_up_f32": (ci, [vp, vp, ci, ci, ci, ci, cf, vp]),
     "pmctf_bilinear_down_f32": (ci, [vp, vp, ci, ci, ci, ci, cf, vp]),
     "pmctf_ew_f32": (ci, [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, vp]),
+    "pmctf_ew_last_launch": (ci, [C.c_char_p, ci]),                               # measurement aid
     "pmctf_spynet_pack8_f32": (ci, [vp, vp, vp, vp, ci, ci, vp]),
     "pmctf_conv3x3_split_supported": (ci, [ci, ci]),
     "pmctf_conv3x3_split_packed_size": (i64, [ci, ci, ci]),

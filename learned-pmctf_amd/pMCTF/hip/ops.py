@@ -301,6 +301,14 @@ def ew(op, a, b=None, alpha=0.0, beta=0.0, out=None):
     return out
 
 
+def ew_last_launch():
+    """Measurement aid: 'kernel expression[ channels| rows] grid G' of the last ew / nearest_up2 / pixel_shuffle2 this thread
+    launched (csrc/ew_ops.hip), '' when that call refused its arguments"""
+    buf = C.create_string_buffer(160)
+    _lib.check(_lib.hip().pmctf_ew_last_launch(buf, 160), "ew_last_launch")
+    return buf.value.decode()
+
+
 def spynet_pack8(im1, warped, flow_up):
     _, _, H, W = im1.shape
     out = empty_nhwc(1, H, W, 8, im1.device)

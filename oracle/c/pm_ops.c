@@ -375,7 +375,10 @@ void pm_flow_warp(const float *im, const float *flow, const float *lin_x, const 
     }
 }
 
-/* avg_pool2d k=2 s=2 (video_net.py:106-108): (((0+a00)+a01)+a10)+a11) / 4 */
+/* avg_pool2d k=2 s=2 (video_net.py:106-108): 0 + ((((0+a00)+a01)+a10)+a11) / 4.  The leading +0 is ATen's accumulator,
+ * the outer one its zeroed output, to which the quotient is added.  Together they move the results that would be -0 and
+ * nothing else: the window of four -0, and a negative sum whose quarter underflows (-2^-149 / 4); both give +0
+ * (tests/test_oracle_ops.py holds this to F.avg_pool2d). */
 void pm_avgpool2(const float *x, float *y, int NC, int H, int W) {
     const int Ho = H / 2, Wo = W / 2;
     for (long job = 0; job < (long)NC * Ho; ++job) {
@@ -384,10 +387,11 @@ void pm_avgpool2(const float *x, float *y, int NC, int H, int W) {
         const float *r0 = x + (nc * H + 2 * oy) * W, *r1 = r0 + W;
         float *o = y + (nc * Ho + oy) * Wo;
         for (int ox = 0; ox < Wo; ++ox) {
-            float s = r0[2 * ox] + r0[2 * ox + 1];
+            float s = 0.0f + r0[2 * ox];
+            s = s + r0[2 * ox + 1];
             s = s + r1[2 * ox];
             s = s + r1[2 * ox + 1];
-            o[ox] = s / 4.0f;
+            o[ox] = 0.0f + s / 4.0f;
         }
     }
 }
@@ -395,8 +399,10 @@ void pm_avgpool2(const float *x, float *y, int NC, int H, int W) {
 /* bilinear x2 upsampling, align_corners=False (video_net.py:58-63, F.interpolate).
  * src = max(0.5*(dst+0.5)-0.5, 0); i0 = floor(src) (<= size-1); l1 = src-i0; l0 = 1-l1;
  * i1 = i0 + (i0 < size-1).  t(row) = fmaf(v[i0], l0x, v[i1]*l1x) ; out = fmaf(t(r0), l0y, t(r1)*l1y)
- * (ATen's CPU kernel evaluates exactly this on planes of >= ~2^15 outputs; on smaller planes it
- * takes another path that differs in the last bit — see tests/test_oracle_ops.py). */
+ * (ATen's CPU kernel evaluates exactly this where it runs its vectorised path: with two or more intra-op threads, from
+ * 40x72 up for x2 / x4 / x8, and on integer-valued planes of any size; on smaller planes of ordinary values, and with one
+ * thread, it takes another order that differs in the last bit.  tests/test_oracle_ops.py asserts the first and records
+ * the counts of the second, DESIGN.md section 2 lists them.) */
 static inline void pm_up_coef(int d, int size, float rf, int *i0, int *i1, float *l0, float *l1) {
     float src = rf * ((float)d + 0.5f) - 0.5f;
     if (src < 0.0f) src = 0.0f;

@@ -506,6 +506,45 @@ CENSUS = [
     ("gemm1x1_below_min_tiles", (2, 32, 13, 37, 56, 1, 1, 0), 0, 2, 0.2, 2, {"MSPLIT_PX": 0},
      [("conv_mfma_pipe_kernel<MT, NT, TW16, 6>", 4, 1, 1)]),]
 
+# ---- rows on special data, derived from the rows above ---------------------------------------------------------------------
+# DATA: row id -> "zeros" | "subnormal" | "nobias"; a row without an entry runs on the ordinary data of case_data.
+#   zeros      the data of valu_conv_census.case_data(..., data="zeros"): column patches of -0, +0, -2^-149 and ordinary
+#              values, weights in [0.25, 0.375), bias -0 — a -0 accumulator next to the padding, where "multiply the padded
+#              zero in" (the oracle's dense convolution, and every kernel here) differs from "skip the tap", and where a
+#              padded k-step, a padded cout row or a masked halo slot shows.  No residual adds: they would bury the zeros.
+#   subnormal  every product and every sum subnormal
+#   nobias     ordinary data, bias = None
+# One zero, one no-bias and one subnormal row per (launched expressions, rule) of the table, each on the geometry, knobs and activation of the first row of the table that launches them with an activation that
+# keeps the sign of a zero (none / relu / leaky; the dispatcher looks at the activation).  The generic kernels are the only
+# ones that take Cin % 16 != 0: they get zero rows at Cin = 8 and Cin = 20, where the last k-step is padded.
+DATA = {}
+N_BASE = len(CENSUS)
+
+
+def _derive():
+    first = {}
+    for r in sorted(CENSUS, key=lambda r: r[3] > 2):                       # stable: rows with act <= leaky first
+        exprs = tuple(e[0] for e in r[7])
+        first.setdefault((exprs, r[2]), r)
+    rows = []
+    for (exprs, rule), r in first.items():
+        rows.append((r[0] + "__zeros", r[1], rule, r[3] if r[3] <= 2 else 0, r[4], 0, r[6], r[7]))
+        DATA[rows[-1][0]] = "zeros"
+        rows.append((r[0] + "__nobias", r[1], r[2], r[3], r[4], r[5], r[6], r[7]))
+        DATA[rows[-1][0]] = "nobias"
+        rows.append((r[0] + "__subnormal", r[1], r[2], r[3] if r[3] <= 2 else 0, r[4], 0, r[6], r[7]))
+        DATA[rows[-1][0]] = "subnormal"
+    for rid in ("gen_nt1_cin8_chain_mt2", "gen_nt1_cin8_blocks_mt7", "gen_nt4_cin8_chain_mt2", "gen_nt2_cin8_blocks_mt7"):
+        r = next(q for q in CENSUS if q[0] == rid)
+        for cin in (8, 20):
+            g = (r[1][0], cin) + r[1][2:]
+            rows.append((f"{rid}__zeros_cin{cin}", g, r[2], r[3], r[4], 0, r[6], r[7]))
+            DATA[rows[-1][0]] = "zeros"
+    return rows
+
+
+CENSUS += _derive()
+
 # Instantiations the library holds that no knob setting reaches: (kernel expression, MT, NT, excluding condition).
 # dispatch_tile<8> calls launch<8, 4, 2> behind run-time conditions, so these kernels are compiled, but every such call
 # sits behind `MTP < 8` (the forced NT = 4 and the large-plane branch alike), and the cout-split path launches MT = 1.
@@ -554,12 +593,65 @@ def out_hw(geometry):
 
 def case_data(r, amplitude=3.0):
     """(x, w, b, [residuals]) of a row, NCHW / OIHW float32, seeded from the row id: x = normal * 3, w = normal * 0.05,
-    b = normal, residuals = normal — the law under which the oracle's summation rules differ in 70 - 96 % of the elements"""
+    b = normal, residuals = normal — the law under which the oracle's summation rules differ in 70 - 96 % of the elements.
+    Rows named in DATA: the zero / subnormal data of valu_conv_census.case_data (one generator for both censuses), or no
+    bias (b = None)."""
     rid, (N, Cin, H, W, Cout, K, S, pad), rule, act, slope, nres, knobs, expected = r
+    kind = DATA.get(rid, "normal")
+    if kind in ("zeros", "subnormal"):
+        import valu_conv_census as vc
+        d = vc.case_data((rid, "dense", (N, Cin, H, W, Cout, K, K, S, pad, pad), rule, act, slope, nres, True, None, None,
+                          {"data": kind}))
+        return d["x"], d["w"], d["b"], d["res"]
     g = np.random.default_rng(zlib.crc32(rid.encode()))
     x = g.standard_normal((N, Cin, H, W), dtype=np.float32) * np.float32(amplitude)
     w = g.standard_normal((Cout, Cin, K, K), dtype=np.float32) * np.float32(0.05)
     b = g.standard_normal(Cout, dtype=np.float32)
     Ho, Wo = out_hw(r[1])
     res = [g.standard_normal((N, Cout, Ho, Wo), dtype=np.float32) for _ in range(nres)]
-    return x, w, b, res
+    return x, w, (None if kind == "nobias" else b), res
+
+
+def skipping_conv(x, w, b, S, pad, rule):
+    """the convolution as a kernel that SKIPS the taps outside the image would compute it (what the depthwise oracle does,
+    and what no dense kernel may do), from the oracle itself.  Skipping a tap is adding a product of -0, the one addend that
+    changes no accumulator (+0 + -0 = +0, -0 + -0 = -0): with the positive weights of the zero data that is the oracle's
+    convolution, without padding, of the image extended by pixels of -0."""
+    from pmctf_oracle import clib
+    assert (w > 0).all()
+    xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)), constant_values=np.float32(-0.0))
+    assert pad == 0 or np.signbit(xp[0, 0, 0, 0])
+    return clib.conv2d(xp, w, b, S, (0, 0), rule)
+
+
+# ---- zero data through the per-class padding of pmctf_conv2d_nhwc_geom_f32 ---------------------------------------------------
+# ops.conv_at_class evaluates a 'same' 3x3 convolution at the positions (2i + py, 2j + px) of one parity class: stride 2,
+# top / left padding 1 - py / 1 - px, so class 0 has a halo above and to the left only and class 3 below and to the right
+# only — one edge where a zero of the padding is multiplied in and one where there is none.
+# (id, (N, Cin, H, W, Cout), rule): a small plane (the cout-split path) and the 2x130x130 plane of the s2_whole exception
+# (at least 8 000 output pixels and 7 cout tiles: the stride-2 pipelined kernel with every cout tile per workgroup).
+GEOM_ZERO = [(f"geom_{name}_rule{rule}", g, rule) for name, g in (("small", (2, 32, 14, 38, 24)), ("s2_whole", (2, 16, 130, 130, 112)))
+             for rule in (0, 1)]
+
+
+def geom_zero_data(case):
+    """(x, w, b) of a GEOM_ZERO case: the zero data of the censuses' one generator, its three patches repeated on the
+    last columns, so that the right edge (padded by the odd-column classes only) lies in zeros too: in the -2^-149 patch,
+    the one that shows a padded last tap where the chain starts at +0"""
+    import valu_conv_census as vc
+    rid, (N, Cin, H, W, Cout), rule = case
+    d = vc.case_data((rid, "dense", (N, Cin, H, W, Cout, 3, 3, 1, 1, 1), rule, 0, 0.0, 0, True, None, None, {"data": "zeros"}))
+    x, p = d["x"], vc.zero_patches(3)[2][1]
+    assert W >= 3 * p
+    x[..., W - p:] = x[..., :p]
+    return x, d["w"], d["b"]
+
+
+def geom_zero_reference(case):
+    """-> ({cls: the oracle's full convolution at the positions of the class}, {cls: the same from a kernel that skipped the
+    taps outside the image})"""
+    from pmctf_oracle import clib
+    x, w, b = geom_zero_data(case)
+    full, skipped = clib.conv2d(x, w, b, 1, (1, 1), case[2]), skipping_conv(x, w, b, 1, 1, case[2])
+    cut = lambda y, cls: np.ascontiguousarray(y[:, :, (cls >> 1)::2, (cls & 1)::2])
+    return {cls: cut(full, cls) for cls in range(4)}, {cls: cut(skipped, cls) for cls in range(4)}

@@ -60,15 +60,60 @@ def pu_reference(x, layers, rule):
 @functools.lru_cache(maxsize=None)
 def reference(shape, scale, rule, skip_rule, mode):
     """mode 0: {c: out};  mode 1: {sign: out}.  float32 steps in the kernel's order.  Plus the saturated share."""
-    from pmctf_oracle import clib
     layers, lift = weights(scale)
-    x0, x1, other = inputs(shape, scale)
+    return compose(inputs(shape, scale), layers, lift, rule, skip_rule, mode)
+
+
+def compose(data, layers, lift, rule, skip_rule, mode):
+    from pmctf_oracle import clib
+    x0, x1, other = data
     if mode == 0:
         pu, sat = pu_reference(x0, layers, rule)
         return {c: (x0 + pu * F(0.1)) * F(c) for c in MODE0_C}, sat
-    N, H, W = shape
     xp = np.pad(x1, ((0, 0), (0, 0), (1, 1), (0, 0)), mode="reflect")
     skip = clib.conv2d(xp, np.array(lift[:3], F).reshape(1, 1, 3, 1), np.array([lift[3]], F), 1, (0, 0), skip_rule)
     pu, sat = pu_reference(skip / F(256), layers, rule)
     br = skip + (pu * F(256)) * F(0.1)
     return {1.0: other + br, -1.0: other - br}, sat
+
+
+# ---- zeros of both signs ---------------------------------------------------------------------------------------------------
+# The kernel masks every layer's halo to 0 by hand and starts its chains at `rule ? 0.0f : bias`: the data on which a masked
+# slot, a skipped tap or a chain started at the wrong zero shows is the zero data of the two convolution censuses
+# (valu_conv_census.case_data(..., data="zeros")): column patches of -0, +0, -2^-149 and ordinary values, every weight in
+# [0.25, 0.375), every bias -0 — the lifting filter's too.  With them a -0 patch stays -0 through all four layers, both
+# tanh, the residual add and the lifting arithmetic, except where a zero of a halo is multiplied in.  `other` has the same
+# patches, so that other +- branch keeps the sign.  "today": the same inputs under the weights and biases of weights(0.1).
+ZERO_SHAPES = [(2, 9, 33), (1, 37, 53)]
+ZERO_BIASES = ["neg0", "today"]
+
+
+def _zero_plane(shape, seed):
+    import valu_conv_census as vc
+    N, H, W = shape
+    # patches as for a 9x9 filter (10 columns each): four 3x3 layers in a row reach four columns into a patch from either side
+    return vc.case_data((seed, "dense", (N, 1, H, W, 1, 9, 9, 1, 4, 4), 0, 0, 0.0, 0, True, None, None, {"data": "zeros"}))["x"]
+
+
+@functools.lru_cache(maxsize=None)
+def zero_inputs(shape):
+    """(x for mode 0, x for mode 1, other): three planes of the zero data"""
+    return tuple(_zero_plane(shape, f"pu_fused_{k}_{shape}") for k in ("x0", "x1", "other"))
+
+
+@functools.lru_cache(maxsize=None)
+def zero_weights(biases):
+    if biases == "today":
+        return weights(0.1)
+    g = np.random.default_rng(5)
+    neg0 = lambda n: np.full(n, -0.0, F)
+    layers = tuple(((F(0.25) + g.random((co, ci, 3, 3), dtype=F) * F(0.125)).astype(F), neg0(co))
+                   for ci, co in ((1, 16), (16, 16), (16, 16), (16, 1)))
+    lift = (F(0.25) + g.random(3, dtype=F) * F(0.125)).astype(F)
+    return layers, (float(lift[0]), float(lift[1]), float(lift[2]), -0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def zero_reference(shape, biases, rule, skip_rule, mode):
+    layers, lift = zero_weights(biases)
+    return compose(zero_inputs(shape), layers, lift, rule, skip_rule, mode)[0]

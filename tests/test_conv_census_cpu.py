@@ -5,6 +5,7 @@ default."""
 import os
 import re
 
+import numpy as np
 import pytest
 
 import conv_census as cc
@@ -156,3 +157,97 @@ def test_case_data_follows_the_row_id():
     assert len(a[3]) == 2 and a[3][0].shape == (2, 8, 13, 37) and a[0].dtype == a[1].dtype == a[3][1].dtype
     again = cc.case_data(cc.row("wave33_nbuf1_mt1"))
     assert all((p == q).all() for p, q in zip(a[:3], again[:3]))
+
+
+# ---- the rows on special data (conv_census.DATA) --------------------------------------------------------------------------
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def test_every_expression_has_its_special_rows():
+    """a zero, a no-bias and a subnormal row per launched expressions and rule the table runs them under; zero rows with a padded last k-step (Cin = 8 and 20) for the two generic kernels, the only ones that take
+    Cin % 16 != 0, under both rules"""
+    base = cc.CENSUS[:cc.N_BASE]
+    assert not any(r[0] in cc.DATA for r in base) and all(r[0] in cc.DATA for r in cc.CENSUS[cc.N_BASE:])
+    kinds = {}
+    for r in cc.CENSUS[cc.N_BASE:]:
+        kinds.setdefault(cc.DATA[r[0]], set()).add((tuple(e[0] for e in r[7]), r[2]))
+    every = {(tuple(e[0] for e in r[7]), r[2]) for r in base}
+    assert kinds["zeros"] == kinds["nobias"] == kinds["subnormal"] == every
+    padded = [r for r in cc.CENSUS if cc.DATA.get(r[0]) == "zeros" and r[1][1] % 16]
+    assert {(r[1][1], r[2], r[7][0][0]) for r in padded} == {(cin, rule, expr) for cin in (8, 20) for rule, expr in (
+        (0, "conv_mfma_kernel<MT, NT, TW16>"), (1, "conv_mfma_bsum_kernel<MT, NT, TW16>"))}
+    assert {r[7][0][2] for r in padded} >= {1, 2, 4}                      # on every tile shape
+    for r in cc.CENSUS[cc.N_BASE:]:
+        if cc.DATA[r[0]] != "nobias":
+            assert r[5] == 0 and r[3] <= 2, r[0]                           # nothing that buries the sign of a zero
+    assert cc.case_data(cc.row("wave33_nbuf1_mt1__nobias"))[2] is None
+
+
+@pytest.mark.parametrize("rid", [r[0] for r in cc.CENSUS if cc.DATA.get(r[0]) in ("zeros", "subnormal")])
+def test_precondition_of_the_special_row(rid):
+    """zero rows: the plane has a border and an interior, the data is the shared generator's (-0 bias, the three patches),
+    the oracle's output holds both signs of zero, and a kernel that skipped the taps outside the image instead of
+    multiplying their zeros in would give other bits in at least one element of the border.  Subnormal rows: a subnormal
+    result."""
+    import valu_conv_census as vc
+    from pmctf_oracle import clib
+    r = cc.row(rid)
+    (N, Cin, H, W, Cout, K, S, pad), rule = r[1], r[2]
+    x, w, b, res = cc.case_data(r)
+    out = clib.conv2d(x, w, b, S, (pad, pad), rule)
+    if cc.DATA[rid] == "subnormal":
+        assert vc.is_subnormal(out).any()
+        return
+    u = _bits(x)
+    (a0, a1), (b0, b1), (c0, c1) = vc.zero_patches(K)
+    assert (u[..., a0:a1] == 0x80000000).all() and (u[..., b0:b1] == 0).all() and (u[..., c0:c1] == 0x80000001).all()
+    assert (_bits(b) == 0x80000000).all() and (w >= 0.25).all() and (w <= 0.375).all() and not res
+    assert H >= 3 and W > c1
+    o = _bits(out)
+    assert (o == 0x80000000).any() and (o == 0).any(), f"{rid}: the oracle's output lacks a sign of zero"
+    if pad:
+        Ho, Wo = cc.out_hw(r[1])
+        assert Ho >= 3 and Wo >= 3
+        border = np.ones((Ho, Wo), bool)
+        border[1:-1, 1:-1] = False
+        skipped = _bits(cc.skipping_conv(x, w, b, S, pad, rule))
+        differs = o != skipped
+        assert differs[..., border].any(), f"{rid}: skipping the padded taps gives the oracle's bits on the whole border"
+        # whatever differs, differs in the sign of a zero and in nothing else
+        assert ((o[differs] | 0x80000000) == 0x80000000).all() and ((skipped[differs] | 0x80000000) == 0x80000000).all()
+
+
+def test_skipping_conv_is_the_depthwise_oracle():
+    """the construction behind the precondition, against the one oracle that does skip: on one channel the dense
+    convolution of the -0-extended image equals the depthwise convolution, bit for bit"""
+    import valu_conv_census as vc
+    from pmctf_oracle import clib
+    r = cc.row("wave33_nbuf1_mt1__zeros")
+    x, w, b, _ = cc.case_data(r)
+    x1, w1, b1 = x[:, :1], w[:1, :1], b[:1]
+    assert (_bits(cc.skipping_conv(x1, w1, b1, 1, 1, 0)) == _bits(clib.dwconv2d(x1, w1, b1))).all()
+    assert (_bits(clib.conv2d(x1, w1, b1, 1, (1, 1), 0)) != _bits(clib.dwconv2d(x1, w1, b1))).any()
+
+
+@pytest.mark.parametrize("case", cc.GEOM_ZERO, ids=[c[0] for c in cc.GEOM_ZERO])
+def test_precondition_of_the_per_class_zero_cases(case):
+    """per parity class: the oracle's output holds both signs of zero; a kernel that skipped the taps outside the image
+    would differ from it on the edges the class pads (class 0: the first row and column, class 3: the last; under rule
+    blocks only on the last ones: class 0 is then a case where skipping and multiplying agree) and, away from the image's
+    corners, on no edge it does not pad; whatever differs, differs in the sign of a zero only"""
+    ref, skipped = cc.geom_zero_reference(case)
+    for cls in range(4):
+        py, px = cls >> 1, cls & 1
+        o, s = _bits(ref[cls]), _bits(skipped[cls])
+        assert (o == 0x80000000).any() and (o == 0).any(), (case[0], cls)
+        d = o != s
+        assert ((o[d] | 0x80000000) == 0x80000000).all() and ((s[d] | 0x80000000) == 0x80000000).all()
+        padded_row, bare_row = (-1, 0) if py else (0, -1)
+        padded_col, bare_col = (-1, 0) if px else (0, -1)
+        # Under the chain from the bias (-0) any padded zero turns the sum to +0.  Where the chain starts at +0 the sign of
+        # a sum of zeros is that of its last tap: a padded tap shows only where it comes after the image's, below or right.
+        rule = case[2]
+        assert d[..., padded_row, 1:-1].any() == (rule == 0 or py == 1), (case[0], cls)
+        assert d[..., 1:-1, padded_col].any() == (rule == 0 or px == 1), (case[0], cls)
+        assert not d[..., 1:-1, 1:-1].any() and not d[..., bare_row, 1:-1].any() and not d[..., 1:-1, bare_col].any(), (case[0], cls)

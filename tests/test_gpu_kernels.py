@@ -19,13 +19,24 @@ def nchw(t):  # torch NHWC device -> numpy NCHW
 
 
 def assert_same(a, b, what):
+    """float32 arrays as bit patterns: -0 is not +0, and two NaNs are equal whatever their payloads (math_sweep.compare);
+    integer arrays by value"""
     a = np.asarray(a); b = np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    if a.dtype == np.float32:
+        import math_sweep as ms
+        ua, ub = np.ascontiguousarray(a).view(np.uint32).reshape(-1), np.ascontiguousarray(b).view(np.uint32).reshape(-1)
+        count, first, _ = ms.compare(ua, ub)
+        if count:
+            i = np.unravel_index(first, a.shape)
+            raise AssertionError(f"{what}: {count} / {a.size} bit patterns differ; first at {tuple(int(k) for k in i)}: "
+                                 f"{a[i]!r} ({int(ua[first]):#010x}) vs {b[i]!r} ({int(ub[first]):#010x})")
+        return
     neq = a != b
     if neq.any():
         i = np.argwhere(neq)[0]
         raise AssertionError(f"{what}: {neq.sum()} / {a.size} elements differ; first at {tuple(i)}: "
-                             f"{a[tuple(i)]!r} vs {b[tuple(i)]!r}; max abs diff {np.abs(a - b).max()}")
+                             f"{a[tuple(i)]!r} vs {b[tuple(i)]!r}")
 
 
 CONV_CASES = [
@@ -385,6 +396,26 @@ def test_conv_at_parity_class_under_the_block_rule(cuda, shape):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("case", __import__("conv_census").GEOM_ZERO, ids=lambda c: c[0])
+def test_conv_at_parity_class_on_zeros_of_both_signs(cuda, case):
+    """the per-class padding of pmctf_conv2d_nhwc_geom_f32 (stride 2, a halo on one side only) on the zero data of the
+    convolution censuses: all four classes under the case's rule are the oracle's full convolution at the positions of the
+    class, bit for bit — the padded zero multiplied in on the edge the class pads, no tap invented on the other.  The
+    preconditions (both zero signs; a skipping kernel would show on the padded edge) are asserted without a GPU in
+    test_conv_census_cpu.py."""
+    import conv_census as cc
+    from pMCTF.hip import ops
+    rid, (n, cin, h, w, cout), rule = case
+    x, wt, b = cc.geom_zero_data(case)
+    ref, _ = cc.geom_zero_reference(case)
+    conv = ops.Conv2d(torch.from_numpy(wt), torch.from_numpy(b), 1, (1, 1), rule=rule)
+    assert not conv.small and not conv.few and not conv.split
+    xt = nhwc(x)
+    for cls in range(4):
+        assert_bits(nchw(ops.conv_at_class(conv, xt, cls)), ref[cls], f"{rid} class {cls}")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(2, 8, 5, 7), (1, 6, 9, 4), (3, 64, 6, 10), (1, 3, 4, 4)])
 def test_nearest_up2_and_pixel_shuffle2_are_exact_copies(cuda, shape):
     """nearest x2 upsampling and nn.PixelShuffle(2) on NHWC (scalar and 16-byte forms: C % 4 == 0 or not) against the torch
@@ -402,36 +433,12 @@ def test_nearest_up2_and_pixel_shuffle2_are_exact_copies(cuda, shape):
     assert_same(nchw(ps), F.leaky_relu(F.pixel_shuffle(torch.from_numpy(x4), 2), 0.1).numpy(), "pixel_shuffle2 + leaky")
 
 
-def _ew_expected(op, a, b, alpha, beta, ops):
-    """numpy float32 restatement of ew_apply (one rounding per written operation)"""
-    from pmctf_oracle import clib
-    f = np.float32
-    al, be = f(alpha), f(beta)
-    if op == ops.EW_COPY: return a.copy()
-    if op == ops.EW_ADD: return a + b
-    if op == ops.EW_SUB: return a - b
-    if op == ops.EW_MUL: return a * b
-    if op == ops.EW_DIV: return a / b
-    if op == ops.EW_MULS: return a * al
-    if op == ops.EW_DIVS: return a / al
-    if op == ops.EW_ADD_MULS: return a + b * al
-    if op == ops.EW_SUB_MULS: return a - b * al
-    if op == ops.EW_ADD_MULS_MULS: return (a + b * al) * be
-    if op == ops.EW_CLAMP_MULS: return np.clip(a * al, -be, be)
-    if op == ops.EW_ROUND_CLAMP_MULS: return np.rint(np.clip(a * al, -be, be))
-    if op == ops.EW_ROUND: return np.rint(a)
-    if op == ops.EW_LEAKY: return np.where(a > 0, a, a * al).astype(f)
-    if op == ops.EW_ADD_MULS2: return a + (b * al) * be
-    if op == ops.EW_SUB_MULS2: return a - (b * al) * be
-    if op == ops.EW_ROUND_CLAMP: return np.rint(np.clip(a, al, be))
-    if op == ops.EW_TANH: return clib.tanh(a)
-    raise AssertionError(op)
-
-
 def test_elementwise_ops_every_layout(cuda):
     """pmctf_ew_f32 over the operand layouts the engine hands it — whole planes and whole NHWC tensors (the flat 16-byte
     form, with and without a vector tail), channel slices of NHWC tensors, row / column windows, a broadcast second
-    operand, in place — every op against a numpy float32 restatement: bit-exact."""
+    operand, in place — every op against a numpy float32 restatement: bit-exact.  (Which kernel each layout reaches, and
+    the special values, are the business of tests/ew_census.py.)"""
+    import ew_census as ec
     from pMCTF.hip import ops
     r = _rng(99)
 
@@ -462,7 +469,7 @@ def test_elementwise_ops_every_layout(cuda):
         assert tuple(ta.shape) == shape
         for op in range(18):
             alpha, beta = (0.37, 2.25) if op != ops.EW_ROUND_CLAMP else (-2.0, 3.0)
-            want = _ew_expected(op, a, b, alpha, beta, ops)
+            want = ec.expected(op, a, b, alpha, beta)                  # the restatement of the census, pinned to torch there
             got = ops.ew(op, ta, tb if op in binary else None, alpha, beta)
             assert_same(got.cpu().numpy(), want, f"ew op {op} on {name} {shape}")
         # second operand broadcast over the planes (stride 0), and the result written over the first operand
@@ -566,7 +573,7 @@ GRID_CAP = 16384 * 256
 
 
 def assert_bits(a, b, what):
-    """assert_same on the bit patterns: tells -0 from +0"""
+    """every bit pattern equal, NaN payloads included"""
     assert_same(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32), what)
 
 

@@ -124,7 +124,7 @@ WRAPPERS = {
     "pmctf_planes_to_u8": "planes_to_u8",
     "pmctf_conv2d_smallcin_f32": "Conv2d", "pmctf_conv3x3_cin1_dual_f32": "conv3x3_cin1_dual",
     "pmctf_conv2d_fewcout_supported": "Conv2d", "pmctf_conv2d_fewcout_f32": "Conv2d",
-    "pmctf_valu_conv_last_launch": "valu_conv_last_launch",
+    "pmctf_valu_conv_last_launch": "valu_conv_last_launch", "pmctf_ew_last_launch": "ew_last_launch",
     "pmctf_dwconv2d_nhwc_f32": "DepthwiseConv2d", "pmctf_flow_warp_f32": "flow_warp", "pmctf_avgpool2_f32": "avgpool2",
     "pmctf_bilinear_up_f32": "bilinear_up2", "pmctf_bilinear_down_f32": "bilinear_down2",
     "pmctf_bilinear_up2_f32": "bilinear_up2", "pmctf_bilinear_down2_f32": "bilinear_down2",

@@ -4,7 +4,9 @@ import itertools
 
 import pytest
 
-from pu_fused_reference import MODE0_C, RULES, SCALES, reference
+import numpy as np
+
+from pu_fused_reference import MODE0_C, RULES, SCALES, ZERO_SHAPES, reference, zero_inputs, zero_reference
 
 
 @pytest.mark.parametrize("scale", list(SCALES), ids=list(SCALES))
@@ -28,3 +30,25 @@ def test_references_tell_the_rules_apart(scale):
             sat = reference(shape, s, 0, 0, mode)[1]
             print(f"mode {mode}: saturated tanh values {sat:.3f}")
             assert sat > 0.5, (mode, sat)
+
+
+@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_zero_references_hold_both_signs_of_zero(shape):
+    """Precondition of the zero cases, on the CPU, per output: every output holds +0; which hold -0 follows from the
+    arithmetic and is asserted as such.  A chain that starts at the bias (-0) keeps a -0 through all four layers, a chain
+    that starts at +0 ends at +0 on zeros.  So mode 0 (x + pu * 0.1) shows -0 under rule chain only; mode 1 with sign +1
+    (other + branch) only where the four layers AND the lifting filter run the chain; mode 1 with sign -1
+    (other - branch: -0 - +0) under every pair.  Every (rule, skip_rule) pair therefore has an output with both signs;
+    mode 0 under rule blocks has none, and checks there that nothing but +0 comes out of a zero patch."""
+    u = zero_inputs(shape)[0].view(np.uint32)
+    assert (u[..., 0:10] == 0x80000000).all() and (u[..., 10:20] == 0).all() and (u[..., 20:30] == 0x80000001).all()
+    for rule, skip_rule in RULES:
+        cases = [((1, sign), out, sign == -1.0 or (rule == 0 and skip_rule == 0))
+                 for sign, out in zero_reference(shape, "neg0", rule, skip_rule, 1).items()]
+        if skip_rule == 0:
+            cases += [((0, c), out, rule == 0) for c, out in zero_reference(shape, "neg0", rule, 0, 0).items()]
+        for key, out, shows_minus_zero in cases:
+            o = np.ascontiguousarray(out).view(np.uint32)
+            assert (o == 0).any(), (rule, skip_rule, key)
+            assert bool((o == 0x80000000).any()) == shows_minus_zero, (rule, skip_rule, key)
+        assert any(c[2] for c in cases if c[0][0] == 1), (rule, skip_rule)
