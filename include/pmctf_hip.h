@@ -518,6 +518,27 @@ int pmctf_resize_yuv420_u16(const uint16_t *src, uint16_t *dst, int h_in, int w_
                             void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Chroma format conversion (csrc/picture_chroma.hip): one packed planar picture of h x w in format fmt_in ->
+ * the picture in fmt_out, both given as 420, 422 or 444 (Y of h x w, then Cb and Cr of h/sy x w/sx each with (sx, sy) =
+ * (2,2), (2,1), (1,1), as the picture lies in a .yuv or .y4m file).  Replaces an outside tool's chroma conversion on the
+ * way into and out of the codec; nothing in the reference.  Bytes for the u8 entry (bitdepth 8), 16-bit samples of
+ * bitdepth 9..16 for the u16 entry; max = 2^bitdepth - 1.
+ *   Y is copied, 16 bytes per thread where the distance between src and dst allows.  Cb and Cr each go through the two
+ *   passes of pmctf_resize_yuv420_u8 above with chroma_x (w/sx_in -> w/sx_out) and chroma_y (h/sy_in -> h/sy_out): tables
+ *   in that layout, in DEVICE memory, 4-byte aligned, built on the host (pmctf_chroma.chroma_tables); taps: their two T,
+ *   an array on the HOST, each 1..17.  An axis whose length does not change has the single-tap table (start[i] = i,
+ *   coef[i] = {16384}), whose pass is exact; the kernel does not read it.  Every index taken from a table is clamped
+ *   before use; start must not decrease along a table.  fmt_in == fmt_out copies the picture.
+ * One launch, nothing intermediate in global memory, no synchronisation.  PMCTF_EINVAL, before the launch and with dst
+ * untouched, for a null pointer, a side that is odd, not positive or above 16384, a format other than the three, a tap
+ * count outside 1..17, a bitdepth the entry does not take, src or dst less aligned than a sample, a table less aligned
+ * than 4 bytes. */
+int pmctf_convert_chroma_u8(const uint8_t *src, uint8_t *dst, int h, int w, int fmt_in, int fmt_out, const void *chroma_x,
+                            const void *chroma_y, const int taps[2], int bitdepth, void *stream);
+int pmctf_convert_chroma_u16(const uint16_t *src, uint16_t *dst, int h, int w, int fmt_in, int fmt_out,
+                             const void *chroma_x, const void *chroma_y, const int taps[2], int bitdepth, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Sequence structure pre-analysis (csrc/scene_ops.hip): the luma histogram of one picture and its sum of absolute
  * differences against the previous one, the figures pmctf_seq.scene_cuts decides scene changes from.
  *

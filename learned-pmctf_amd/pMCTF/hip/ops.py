@@ -825,6 +825,52 @@ def resize_yuv420(frame, h_in, w_in, h_out, w_out, tables, taps, bitdepth=8):
 
 
 # ------------------------------------------------------------------------------------------------
+# chroma format conversion of packed pictures (csrc/picture_chroma.hip)
+CHROMA_SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}            # format -> (sx, sy)
+
+
+def chroma_frame_samples(h, w, fmt):
+    """samples of one packed h x w picture of chroma format "420", "422" or "444" """
+    if fmt not in CHROMA_SUBSAMPLING:
+        raise ValueError(f"a chroma format is one of {sorted(CHROMA_SUBSAMPLING)} (got {fmt!r})")
+    sx, sy = CHROMA_SUBSAMPLING[fmt]
+    return h * w + 2 * (h // sy) * (w // sx)
+
+
+def convert_chroma(frame, h, w, fmt_in, fmt_out, tables, taps, bitdepth=8):
+    """One packed planar h x w picture of chroma format fmt_in ("420", "422", "444"; uint8 device tensor at bitdepth 8,
+    uint16 at 9..16) -> the packed picture of fmt_out, same type: Y copied, Cb and Cr through the integer filter of DESIGN
+    5l / 5m.  tables: the chroma planes' x and y axis tables as uint8 device tensors in the layout
+    pmctf_scale.device_table uploads (pmctf_chroma.chroma_tables), taps: their two tap counts.  One launch."""
+    h, w = _picture_size(h, w)
+    bitdepth = int(bitdepth)
+    dtype = torch.uint8 if bitdepth == 8 else torch.uint16
+    if bitdepth != 8:
+        _bitdepth(bitdepth)
+    n_in, n_out = chroma_frame_samples(h, w, fmt_in), chroma_frame_samples(h, w, fmt_out)
+    if not isinstance(frame, torch.Tensor) or frame.dtype != dtype:
+        raise ValueError(f"expect a {dtype} tensor at bitdepth {bitdepth}")
+    if frame.numel() != n_in:
+        raise ValueError(f"a {h}x{w} {fmt_in} picture has {n_in} samples, got {frame.numel()}")
+    dev = _dev(frame)
+    frame = frame.contiguous()
+    taps = [int(t) for t in taps]
+    if len(tables) != 2 or len(taps) != 2:
+        raise ValueError("expect two tables and two tap counts: chroma x, chroma y")
+    (sx, sy) = CHROMA_SUBSAMPLING[fmt_out]
+    for t, rows, n in zip(tables, (w // sx, h // sy), taps):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not 1 <= n <= 17 or t.numel() != rows * (4 + 2 * n):
+            raise ValueError(f"a table of {rows} rows of {n} taps is a uint8 tensor of {rows * (4 + 2 * n)} bytes, 1..17 taps")
+        if _dev(t) != dev:
+            raise ValueError("the tables live on the picture's device")
+    out = torch.empty(n_out, dtype=dtype, device=dev)
+    fn = _lib.hip().pmctf_convert_chroma_u8 if bitdepth == 8 else _lib.hip().pmctf_convert_chroma_u16
+    _lib.check(fn((_pu8 if bitdepth == 8 else _pu16)(frame), C.c_void_p(out.data_ptr()), h, w, int(fmt_in), int(fmt_out),
+                  *(_pu8(t.contiguous()) for t in tables), (C.c_int * 2)(*taps), bitdepth, _stream()), "convert_chroma")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # sequence structure pre-analysis (csrc/scene_ops.hip)
 def luma_activity(cur, prev, bitdepth=8, hist=None, sad=None):
     """The luma histogram of one picture and its sum of absolute differences against the previous one, in integers at

@@ -481,7 +481,8 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
 def _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
                      skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
                      picture_hash=None, bitdepth=8, keep_gops=False, msssim=False, scale=None):
-    """encode_sequence's body; scale: a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence)"""
+    """encode_sequence's body; scale: a pmctf_scale.CodedSize (pmctf_scale.encode_sequence), a pmctf_chroma.ChromaFormat
+    (pmctf_chroma.encode_sequence: it also opens the reader of its source) or None"""
     import io
     import time
     if picture_hash is not None and picture_hash not in HASH_LEVELS:
@@ -513,7 +514,8 @@ def _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bi
         if len(reader) < frame_num:
             raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
     else:
-        reader = YUVReader(yuv_path, width, height, start_index=0, bitdepth=bitdepth)
+        reader = (getattr(scale, "open_reader", None) or YUVReader)(yuv_path, width, height, start_index=0,
+                                                                    bitdepth=bitdepth)
     display = []
     if scale is not None:
         reader.resample = scale.ingest(keep=True)
@@ -1124,13 +1126,20 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     to that display size on the device before it is written, .yuv and PNGs alike; the hashes are those of the coded-size
     pictures and are checked before.  pmctf_scale.decode_sequence_checked(..., coded_size_output=True) writes the
     coded-size pictures instead.
+    A folder with a source_format.json (pmctf_chroma: a .y4m source, or one that is not 4:2:0) is then written in the chroma
+    format of its source, converted on the device, and a yuv_out ending in .y4m as a Y4M file (header, FRAME markers);
+    pmctf_chroma.decode_sequence_checked(..., coded_format_output=True) writes the coded 4:2:0 pictures.  PNGs and hashes
+    are those of the 4:2:0 pictures either way.
     Returns decode_sequence's dict: "verified" counts the pictures checked, "hash_mismatches" lists {"gop", "folder",
     "frame", "plane", "decoded", "recorded"}; "frames" holds the written sizes."""
     return _decode_sequence(codec, bin_folder, yuv_out, device, png_out, verify)
 
 
-def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", coded_size_output=False):
-    """decode_sequence_checked's body; coded_size_output: pmctf_scale.decode_sequence_checked"""
+def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", coded_size_output=False,
+                     coded_format_output=False):
+    """decode_sequence_checked's body; coded_size_output: pmctf_scale.decode_sequence_checked; coded_format_output:
+    pmctf_chroma.decode_sequence_checked (a folder with a source_format.json is written in its source's chroma format, a
+    yuv_out ending in .y4m as a Y4M file)"""
     import contextlib
     import time
     if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
@@ -1153,9 +1162,13 @@ def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, veri
     import pmctf_scale
     display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
     out_shape = (h, w) if display is None else display.size[::-1]
+    import pmctf_chroma
+    fmt = pmctf_chroma.output_format(bin_folder, yuv_out, w, h, display, dev, bitdepth, coded_format_output)
     q_indexes = gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, verified = [], [], [], 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
+        if f is not None and fmt is not None:
+            f.write(fmt.stream_header)
         for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, gop_folder(k))
@@ -1169,12 +1182,16 @@ def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, veri
                 mismatches += bad
                 verified += size
             if f is not None:
-                if display is not None:
+                if fmt is not None:
+                    pictures = fmt.pictures(out["frames"])
+                elif display is not None:
                     pictures = display.pictures(out["frames"])
                 else:
                     pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
                         frames_to_u8(out["frames"], h, w)
                 for planes in pictures:
+                    if fmt is not None:
+                        f.write(fmt.frame_marker)
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:

@@ -375,7 +375,8 @@ def _check_against_extract(bin_folder, level, motion_fill):
 
 def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     """Copy what a level-`level` decode of the sequence in src_folder reads into dst_folder (created when missing; refused
-    when not empty): the header, picture_format.json, display_format.json and layer_hashes.json where present, per GOP
+    when not empty): the header, picture_format.json, display_format.json, source_format.json and layer_hashes.json where
+    present, per GOP
     exactly layer_file_names(size, level, motion_fill), and layer_extract.json {"format_version", "min_level": level, "motion":
     motion_fill}, which decode_sequence_layer reads.  picture_hashes.json is not copied: the folder cannot produce those
     pictures.  No codec, no GPU.  -> the relative paths written, sorted."""
@@ -386,8 +387,10 @@ def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     _check_against_extract(src_folder, level, motion_fill)
     if os.path.exists(dst_folder) and (not os.path.isdir(dst_folder) or os.listdir(dst_folder)):
         raise ValueError(f"{dst_folder}: not an empty folder; extract_layer writes into a new or empty one")
+    import pmctf_chroma
     import pmctf_scale
-    copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, pmctf_scale.DISPLAY_FORMAT, LAYER_HASHES)
+    copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, pmctf_scale.DISPLAY_FORMAT,
+                          pmctf_chroma.SOURCE_FORMAT, LAYER_HASHES)
               if os.path.exists(os.path.join(src_folder, n))]
     for k, g in enumerate(gops):
         copies += [os.path.join(G.gop_folder(k), n) for n in layer_file_names(g[1], level, motion_fill)]
@@ -420,15 +423,17 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
     holds no motion files for the left-out stages.
     A folder with a display_format.json has its pictures resampled to the display size after the checks, as
     decode_sequence_checked does; pmctf_scale.decode_sequence_layer(..., coded_size_output=True) writes them
-    as coded.
+    as coded.  A source_format.json and a yuv_out ending in .y4m are honoured as decode_sequence_checked honours them
+    (pmctf_chroma.decode_sequence_layer(..., coded_format_output=True): the coded 4:2:0 pictures).
     Returns decode_sequence's dict ("frames", "seconds", "verified", "hash_mismatches", "header", "bitdepth") plus "level",
     "times": the source index of every written picture, and "bytes_read": the sizes of the files read, layer_bytes."""
     return _decode_sequence_layer(codec, bin_folder, yuv_out, level, device, png_out, verify, motion_fill)
 
 
 def _decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False,
-                           coded_size_output=False):
-    """decode_sequence_layer's body; coded_size_output: pmctf_scale.decode_sequence_layer"""
+                           coded_size_output=False, coded_format_output=False):
+    """decode_sequence_layer's body; coded_size_output: pmctf_scale.decode_sequence_layer; coded_format_output:
+    pmctf_chroma.decode_sequence_layer"""
     import contextlib
     import time
     import torch
@@ -466,10 +471,14 @@ def _decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_o
     import pmctf_scale
     display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
     out_shape = (h, w) if display is None else display.size[::-1]
+    import pmctf_chroma
+    fmt = pmctf_chroma.output_format(bin_folder, yuv_out, w, h, display, dev, bitdepth, coded_format_output)
     q_indexes = G.gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, times = [], [], [], []
     verified = at = nbytes = 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
+        if f is not None and fmt is not None:
+            f.write(fmt.stream_header)
         for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, G.gop_folder(k))
@@ -487,12 +496,16 @@ def _decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_o
                 mismatches += bad
                 verified += len(source)
             if f is not None:
-                if display is not None:
+                if fmt is not None:
+                    pictures = fmt.pictures(out["frames"])
+                elif display is not None:
                     pictures = display.pictures(out["frames"])
                 else:
                     pictures = G.frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
                         G.frames_to_u8(out["frames"], h, w)
                 for planes in pictures:
+                    if fmt is not None:
+                        f.write(fmt.frame_marker)
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:

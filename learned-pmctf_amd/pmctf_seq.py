@@ -303,7 +303,8 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
     sizes of its files, "seconds", ...}; choose returns the trial it accepts, whose files it has moved to
     bin_folder/gop_{k:05d}.  Only the accepted trial is reconstructed, reported and counted in the "average ms" lines; the
     GOP entries then carry "q_index" and the header is format version 2.
-    scale: a pmctf_scale.CodedSize or None.  With one, every reader resamples its pictures on the device after upload
+    scale: a pmctf_scale.CodedSize, a pmctf_chroma.ChromaFormat (which also opens the reader of its source) or None.  With
+    one, every reader resamples its pictures on the device after upload
     (read_gop_device, whatever `ingest` says; the scene-cut pass too), everything below sees a source of the coded size, the
     header included, bin_folder gets display_format.json and the result "display_quality"."""
     import io
@@ -356,7 +357,8 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
             if len(reader) < frame_num:
                 raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
         else:
-            reader = YUVReader(source, width, height, start_index=0, bitdepth=bitdepth)
+            reader = (getattr(scale, "open_reader", None) or YUVReader)(source, width, height, start_index=0,
+                                                                        bitdepth=bitdepth)
         if scale is not None:
             reader.resample = scale.ingest(keep)
         return reader

@@ -20,7 +20,11 @@ indices.  Level 1 and above are checked against layer_hashes.json (tools/encode_
 high-band pictures are taken as zero; that output has no hashes to be checked against.
 A folder coded with --coded-size (it holds display_format.json) is written at the size of its source: every decoded picture
 is resampled there on the GPU after the hashes, which describe the coded-size pictures, have been checked.
---coded-size-output writes the pictures as they were coded instead: the file tools/check_picture_hashes.py checks."""
+--coded-size-output writes the pictures as they were coded instead: the file tools/check_picture_hashes.py checks.
+A folder coded from a .y4m or from a 4:2:2 / 4:4:4 source (it holds source_format.json) is written in the chroma format of
+its source, converted on the GPU after the resampling (pmctf_chroma); --coded-format-output writes the coded
+4:2:0 pictures instead.  An OUT path ending in .y4m becomes a Y4M file (its F tag is the recorded frame rate, 25:1 when
+there is none)."""
 import argparse
 import json
 import os
@@ -49,6 +53,8 @@ def main():
                     help="with --temporal-level: full frame rate, the left-out high bands taken as zero (never verified)")
     ap.add_argument("--coded-size-output", action="store_true",
                     help="a folder coded with --coded-size: write the coded-size pictures, not the display-size ones")
+    ap.add_argument("--coded-format-output", action="store_true",
+                    help="a folder with a source_format.json: write the coded 4:2:0 pictures, not the source's chroma format")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args()
@@ -61,7 +67,7 @@ def main():
         ap.error("give OUT.yuv, --png DIR or both")
     import torch
     import pmctf_gop
-    import pmctf_scale
+    import pmctf_chroma
     from pMCTF.models.video.pMCTF_L import pMCTF
     header, _ = pmctf_gop.sequence_layout(a.bin_folder)
     net = pMCTF(num_me_stages=header["num_me_stages"]).eval()
@@ -76,12 +82,14 @@ def main():
     with torch.no_grad():
         try:
             if layered:
-                out = pmctf_scale.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
-                                                        png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
-                                                        coded_size_output=a.coded_size_output)
+                out = pmctf_chroma.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
+                                                         png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
+                                                         coded_size_output=a.coded_size_output,
+                                                         coded_format_output=a.coded_format_output)
             else:
-                out = pmctf_scale.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
-                                                          verify=a.verify, coded_size_output=a.coded_size_output)
+                out = pmctf_chroma.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
+                                                           verify=a.verify, coded_size_output=a.coded_size_output,
+                                                           coded_format_output=a.coded_format_output)
         except pmctf_gop.PictureHashMismatch as e:
             sys.exit(f"picture hash mismatch: {e}")
     n = len(out["frames"])

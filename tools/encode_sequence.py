@@ -28,7 +28,11 @@ refused.  BIN_FOLDER gets rate_control.json, which tools/check_rate.py checks wi
 --coded-size WxH [--chroma-loc center|left] (pmctf_scale): every picture is resampled to W x H on the GPU before it is
 coded (an exact integer Catmull-Rom filter; each side within a factor of 4 of the source's) and everything
 above applies to the resampled sequence.  BIN_FOLDER/display_format.json keeps the source's size, to which
-tools/decode_sequence.py resamples the decoded pictures; the mean PSNR of those against the source goes to stderr."""
+tools/decode_sequence.py resamples the decoded pictures; the mean PSNR of those against the source goes to stderr.
+SOURCE.y4m (pmctf_chroma): --width, --height, --bitdepth and --fps default from its header, and a 4:2:2 or
+4:4:4 file is converted to 4:2:0 on the GPU by the same filter before it is coded; --chroma-format 420|422|444 says the
+same of a raw planar file.  --chroma-loc then also tells the siting of the source (default: the header's; left for 4:2:2).
+BIN_FOLDER/source_format.json keeps the source's format and frame rate, to which tools/decode_sequence.py converts back."""
 import argparse
 import os
 import sys
@@ -75,19 +79,43 @@ def main(argv=None):
     ap.add_argument("--picture-hash", choices=("u8", "u16", "f32"),
                     help="record picture hashes: of the written planes (u8; u16 with --bitdepth above 8), and of the padded "
                          "float32 reconstructions (f32)")
-    ap.add_argument("--bitdepth", type=int, default=8, help="bit depth of a .yuv source: 8, or 9..16 for 16-bit samples")
+    ap.add_argument("--bitdepth", type=int, help="bit depth of a .yuv source: 8 (default), or 9..16 for 16-bit samples")
+    ap.add_argument("--chroma-format", choices=("420", "422", "444"),
+                    help="chroma format of a raw planar source (default 420; a .y4m says its own)")
     ap.add_argument("--layer-hashes", action="store_true",
                     help="also record the hashes of the temporal layers (layer_hashes.json), from a full decode of the folder")
     ap.add_argument("--coded-size", metavar="WxH", help="code at this size instead of the source's (even, within a factor of 4)")
     ap.add_argument("--chroma-loc", choices=("center", "left"),
                     help="--coded-size: where the source's chroma samples lie (center: the default; left: MPEG-2 siting)")
-    ap.add_argument("source", help=".yuv file or folder of PNGs")
+    ap.add_argument("source", help=".yuv or .y4m file, or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args(argv)
+    import pmctf_chroma
     import pmctf_scale
+    y4m = pmctf_chroma.is_y4m(a.source) and not os.path.isdir(a.source)
+    if y4m:
+        try:
+            head = pmctf_chroma.read_y4m_header(a.source)
+        except (OSError, ValueError) as e:
+            ap.error(f"{a.source}: {e}")
+        for opt, key in (("width", "width"), ("height", "height"), ("bitdepth", "bitdepth"), ("chroma_format", "chroma_format")):
+            if getattr(a, opt) is None:
+                setattr(a, opt, head[key])
+            elif getattr(a, opt) != head[key]:
+                ap.error(f"--{opt.replace('_', '-')} {getattr(a, opt)}: the Y4M header says {head[key]} (C{head['tag']})")
+        if a.fps is None and a.bitrate is not None:
+            a.fps = head["frame_rate"]
+    if a.bitdepth is None:
+        a.bitdepth = 8
+    converted = y4m or a.chroma_format not in (None, "420")
+    if converted:
+        try:
+            pmctf_chroma.resolve_loc(a.chroma_format or "420", a.chroma_loc)
+        except ValueError as e:
+            ap.error(f"--chroma-loc: {e}")
     coded_size = None
     if a.coded_size is None:
-        if a.chroma_loc is not None:
+        if a.chroma_loc is not None and not converted:
             ap.error("--chroma-loc: only with --coded-size")
     else:
         try:
@@ -107,7 +135,7 @@ def main(argv=None):
         if a.structure == "search":
             ap.error("--bitrate with --structure search: the search ranks GOP sizes at one fixed q_index")
         if a.fps is None:
-            ap.error("--bitrate needs --fps")
+            ap.error("--bitrate needs --fps (a .y4m source with an F tag has its own)")
         q_min = 0 if a.q_min is None else a.q_min
         q_max = pmctf_rate.Q_NUM - 1 if a.q_max is None else a.q_max
         rate = dict(q_choices=range(q_min, q_max + 1), q_start=a.q_index,
@@ -132,6 +160,8 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     if os.path.isdir(a.source):
+        if a.chroma_format is not None:
+            ap.error("--chroma-format: for a planar file, PNGs are converted to 4:2:0 as they are")
         src_format, reader = "png", pmctf_gop.PNGReader(a.source)
         width, height, available = reader.width, reader.height, len(reader)
         if (a.width, a.height) not in ((None, None), (width, height)):
@@ -140,8 +170,14 @@ def main(argv=None):
         if a.width is None or a.height is None:
             ap.error("--width and --height are required for a .yuv source")
         src_format, width, height = "yuv", a.width, a.height
-        sample_bytes = 2 if a.bitdepth > 8 else 1
-        available = os.path.getsize(a.source) // ((width * height + 2 * (width // 2) * (height // 2)) * sample_bytes)
+        if converted:
+            try:
+                available = len(pmctf_chroma.PlanarReader(a.source, width, height, 0, a.bitdepth, a.chroma_format))
+            except ValueError as e:
+                ap.error(str(e))
+        else:
+            sample_bytes = 2 if a.bitdepth > 8 else 1
+            available = os.path.getsize(a.source) // ((width * height + 2 * (width // 2) * (height // 2)) * sample_bytes)
     if coded_size is not None:
         try:
             pmctf_scale.check_sizes(width, height, coded_size[0], coded_size[1], what="--coded-size")
@@ -166,25 +202,25 @@ def main(argv=None):
     net.update(force=True)
     os.makedirs(a.bin_folder, exist_ok=True)
     common = dict(src_format=src_format, decoded_frame_path=a.decoded_frames, msssim=a.msssim, picture_hash=a.picture_hash,
-                  bitdepth=a.bitdepth, coded_size=coded_size, chroma_loc=a.chroma_loc or "center")
+                  bitdepth=a.bitdepth, coded_size=coded_size, chroma_loc=a.chroma_loc, chroma_format=a.chroma_format)
     with torch.no_grad():
         if fixed:
-            out = pmctf_scale.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
-                                            keep_gops=True, **common)
+            out = pmctf_chroma.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+                                             keep_gops=True, **common)
         else:
             import pmctf_seq
             cuts = dict(structure=a.structure, hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
                         mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min)
             if rate is not None:
-                out = pmctf_scale.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
-                                                      a.bin_folder, a.device, **cuts, **common, **rate)
+                out = pmctf_chroma.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
+                                                       a.bin_folder, a.device, **cuts, **common, **rate)
                 for k, r in enumerate(out["rate"]):
                     print(f"GOP {k}: q_index {r['q_index']}, {r['bits']} bits of {r['budget']}"
                           f"{'' if r['fits'] else ' (does not fit)'}, {len(r['trials'])} trial(s), credit {r['credit']}",
                           file=sys.stderr)
             else:
-                out = pmctf_scale.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
-                                                       a.device, **cuts, **common)
+                out = pmctf_chroma.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                                                        a.device, **cuts, **common)
             if "cuts" in out:
                 print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
             print("GOPs (first picture: size, motion down-sampling): " +
@@ -197,7 +233,7 @@ def main(argv=None):
             except pmctf_gop.PictureHashMismatch as e:
                 sys.exit(f"picture hash mismatch, no layer hashes written: {e}")
             print(f"layer hashes: {path}", file=sys.stderr)
-    if "display_quality" in out:
+    if out.get("display_quality"):
         mean = {k: sum(q[k] for q in out["display_quality"]) / len(out["display_quality"]) for k in out["display_quality"][0]}
         print(f"coded at {coded_size[0]}x{coded_size[1]}; at {width}x{height} against the source: " +
               ", ".join(f"{k} {v:.4f}" for k, v in mean.items()), file=sys.stderr)
