@@ -134,7 +134,9 @@ __global__ void conv_smallcin_reg_kernel(const float *__restrict__ x, const floa
         for (int ci = 0; ci < CIN; ++ci) wr[t * CIN + ci] = w[(co * CIN + ci) * (K * K) + t];
     const float b = bias ? bias[co] : 0.0f;
     const int npix = N * Ho * Wo;               // < 2^31 on this path (checked by the launcher)
-    for (int p = blockIdx.x * ppp + slot; p < npix; p += gridDim.x * ppp) {
+    // the counter is unsigned: the last p + step (a step is at most 2^22) may pass 2^31 when npix is within one step of it
+    for (unsigned pu = blockIdx.x * ppp + slot; pu < (unsigned)npix; pu += gridDim.x * ppp) {
+        const int p = (int)pu;
         const int ox = p % Wo;
         const int r = p / Wo;
         const int oy = r % Ho;

@@ -556,7 +556,7 @@ __device__ __forceinline__ void conv3x3s1_wave_body(const ConvArgs &a, const int
         const int ly = pix / LW, lx = pix - ly * LW;
         const int gy = iy0 + ly, gx = ix0 + lx;
         ok[j] = e < E && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        goff[j] = ok[j] ? (unsigned)(((gy * a.W + gx) * a.Cin + part * 4) * 4) : 0u;
+        goff[j] = ok[j] ? ((unsigned)(gy * a.W + gx) * (unsigned)a.Cin + (unsigned)(part * 4)) * 4u : 0u;   // < 2^32: the host's guard
         pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const char *xn = (const char *)(a.x + (size_t)n * a.H * a.W * a.Cin);
@@ -743,7 +743,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s1_blocks_tileouter_kernel(Conv
         const int ly = pix / LW, lx = pix - ly * LW;
         const int gy = iy0 + ly, gx = ix0 + lx;
         ok[j] = e < E && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        goff[j] = ok[j] ? (unsigned)(((gy * a.W + gx) * a.Cin + part * 4) * 4) : 0u;
+        goff[j] = ok[j] ? ((unsigned)(gy * a.W + gx) * (unsigned)a.Cin + (unsigned)(part * 4)) * 4u : 0u;   // < 2^32: the host's guard
         pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const char *xn = (const char *)(a.x + (size_t)n * a.H * a.W * a.Cin);
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s1_pipe_kernel(ConvArgs a) {
         const int ly = pix / LW, lx = pix - ly * LW;
         const int gy = iy0 + ly, gx = ix0 + lx;
         ok[j] = e < E && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        goff[j] = ok[j] ? (unsigned)(((gy * a.W + gx) * a.Cin + part * 4) * 4) : 0u;
+        goff[j] = ok[j] ? ((unsigned)(gy * a.W + gx) * (unsigned)a.Cin + (unsigned)(part * 4)) * 4u : 0u;   // < 2^32: the host's guard
         pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const char *xn = (const char *)(a.x + (size_t)n * a.H * a.W * a.Cin);
@@ -1059,7 +1059,7 @@ __global__ __launch_bounds__(256, 2) void conv7x7s1_pipe_kernel(ConvArgs a) {
         const int ly = pix / LW, lx = pix - ly * LW;
         const int gy = iy0 + ly, gx = ix0 + lx;
         ok[j] = e < E && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        goff[j] = ok[j] ? (unsigned)(((gy * a.W + gx) * a.Cin + part * 4) * 4) : 0u;
+        goff[j] = ok[j] ? ((unsigned)(gy * a.W + gx) * (unsigned)a.Cin + (unsigned)(part * 4)) * 4u : 0u;   // < 2^32: the host's guard
         pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const char *xn = (const char *)(a.x + (size_t)n * a.H * a.W * a.Cin);

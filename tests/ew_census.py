@@ -29,9 +29,10 @@ NAMES = ["COPY", "ADD", "SUB", "MUL", "DIV", "MULS", "DIVS", "ADD_MULS", "SUB_MU
 FLAT_V, FLAT_S, TRANSPOSE = "ew_flat_kernel<true>", "ew_flat_kernel<false>", "ew_transpose_kernel"
 C4_CH, C4_ROWS = "ew_c4_kernel<int> channels", "ew_c4_kernel<int> rows"
 GEN_C, GEN_P = "ew_kernel<true, int>", "ew_kernel<false, int>"
-# instantiations no plane of a test's size reaches: they need 2^31 elements (8 GiB per operand)
-UNREACHABLE = {"ew_c4_kernel<long>": "total >= 2^31", "ew_kernel<true, long>": "total >= 2^31",
-               "ew_kernel<false, long>": "total >= 2^31"}
+# instantiations no row of THIS table reaches: they need 2^31 elements (8 GiB per operand) and are rows of the large-plane
+# census (large_planes.py, the "ew_*__over" rows), next to their int neighbours just under 2^31
+LARGE_PLANES = {"ew_c4_kernel<long>": "ew_c4__over", "ew_kernel<true, long>": "ew_cfast__over",
+                "ew_kernel<false, long>": "ew_planar__over"}
 SENT = 0x5A5A5A5A
 PAD = 64                    # sentinel words before and after every view's extent
 

@@ -63,8 +63,13 @@ def instantiated(library, names):
 def test_every_launched_kernel_is_a_rows_expected_kernel(source):
     in_source = launched_expressions(source)
     assert len(in_source) == 15, sorted(in_source)
-    reachable = {e for e in in_source if strip_form(e) not in ec.UNREACHABLE}
-    assert {strip_form(e) for e in in_source - reachable} == set(ec.UNREACHABLE)
+    import large_planes as lp
+    reachable = {e for e in in_source if strip_form(e) not in ec.LARGE_PLANES}
+    assert {strip_form(e) for e in in_source - reachable} == set(ec.LARGE_PLANES)
+    for expr, rid in ec.LARGE_PLANES.items():                   # the 2^31-element forms: rows of the large-plane census
+        assert strip_form(lp.row(rid)[7]) == expr and lp.row(rid)[1] == "ew" and lp.row(rid)[9] == "over", expr
+        under = lp.row(rid.replace("__over", "__under"))
+        assert strip_form(under[7]) == expr.replace("long", "int"), expr
     assert reachable == ec.all_expressions(), (f"without a row: {sorted(reachable - ec.all_expressions())}; "
                                                f"not in the source: {sorted(ec.all_expressions() - reachable)}")
 
@@ -75,9 +80,10 @@ def test_every_instantiation_in_the_library_has_a_row_or_a_reason(source):
     assert kernels == names, sorted(kernels ^ names)
     built = instantiated(LIB, names)
     rows = {strip_form(e) for e in ec.all_expressions()}
-    assert built == rows | set(ec.UNREACHABLE), (f"instantiated without a row: {sorted(built - rows - set(ec.UNREACHABLE))}; "
-                                                 f"in the table, not in the library: {sorted((rows | set(ec.UNREACHABLE)) - built)}")
-    assert not rows & set(ec.UNREACHABLE)
+    large = set(ec.LARGE_PLANES)
+    assert built == rows | large, (f"instantiated without a row: {sorted(built - rows - large)}; "
+                                   f"in the table, not in the library: {sorted((rows | large) - built)}")
+    assert not rows & large
 
 
 def test_conditions_the_rows_sit_next_to(source):

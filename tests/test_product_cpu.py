@@ -67,6 +67,12 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
         assert L.pmctf_math_probe_f32(0, None, 0, n, y, 0.0, None) == -1
     for fn in (-1, 8, 13, 99):                                  # 8 = PMCTF_PROBE_ACT + PMCTF_ACT_NONE: no function
         assert L.pmctf_math_probe_f32(fn, None, 0, 16, y, 0.0, None) == -1
+    # host-side size refusals (large_planes.GUARDS, "refusal"): sizes whose 32-bit indices would wrap, refused before any
+    # launch and before any access — the pointers are made up.  -1 is PMCTF_EINVAL; a failed launch would be -2.
+    import large_planes as lp
+    assert len(lp.REFUSALS) == 4
+    for name, (entry, args) in lp.REFUSALS.items():
+        assert getattr(L, entry)(*[y if a == "P" else a for a in args]) == -1, name
 
 
 def test_product_path_has_no_cpu_fallback():
