@@ -11,22 +11,22 @@ or 4:2:2, +1/4 going back.  4:2:2 is horizontally co-sited (the Y4M / MPEG-2 lay
 is coded as 4:2:0 "left", and "center" with it is a ValueError.  4:4:4 sources default to "center".
 
 This module holds that arithmetic's tables, the Y4M header (parse_y4m_header, y4m_header), PlanarReader (.y4m files and
-raw planar files of any of the three formats), ChromaFormat (what the encoders need: the `scale` object of their bodies,
-wrapping an optional pmctf_scale.CodedSize: format first, size second), source_format.json, OutputFormat (what the
-decoders need) and the entry points encode_sequence, encode_sequence_gops, encode_sequence_rate, decode_sequence_checked,
+raw planar files of any of the three formats), SourcePipeline (what the encoders' bodies take: an optional step to 4:2:0,
+an optional pmctf_scale.CodedSize, format first, size second), source_format.json, OutputFormat (what the decoders need)
+and the entry points encode_sequence, encode_sequence_gops, encode_sequence_rate, decode_sequence_checked,
 decode_sequence_layer: pmctf_scale's functions with the keywords chroma_format (encoding) and coded_format_output
-(decoding) added.  With a raw 4:2:0 source and chroma_format=None they are pmctf_scale's functions.
+(decoding) added.  With a raw 4:2:0 source and chroma_format=None they do what pmctf_scale's functions do.
 
 Out of scope: 4:0:0, 420paldv, 4:1:1, alpha, interlaced material; quality figures in the source's own format (the tables
 are those of the coded 4:2:0 pictures against the converted source)."""
 import functools
-import json
 import os
 import re
 from fractions import Fraction
 
 import pmctf_scale
-from pmctf_scale import CHROMA_LOCS, COEF_ONE, FILTER, MAX_SIDE, _is_int
+from pmctf_records import is_int, read_record, write_record
+from pmctf_scale import CHROMA_LOCS, COEF_ONE, FILTER, MAX_SIDE
 
 FORMATS = ("420", "422", "444")
 SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}            # format -> (sx, sy)
@@ -76,7 +76,7 @@ def resolve_loc(chroma_format, chroma_loc=None):
 
 def check_side(width, height, what="picture"):
     for n in (width, height):
-        if not _is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
+        if not is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
             raise ValueError(f"{what}: sides are even, positive and at most {MAX_SIDE} (got {width!r}x{height!r})")
 
 
@@ -126,7 +126,7 @@ class Converter:
     and uploaded here, once."""
 
     def __init__(self, width, height, fmt_in, fmt_out, device, bitdepth=8, chroma_loc="center"):
-        if not _is_int(bitdepth) or not 8 <= bitdepth <= 16:
+        if not is_int(bitdepth) or not 8 <= bitdepth <= 16:
             raise ValueError(f"bitdepth is 8 or 9..16 (got {bitdepth!r})")
         axes = chroma_axes(width, height, fmt_in, fmt_out, chroma_loc)
         self.size, self.fmt_in, self.fmt_out = (width, height), fmt_in, fmt_out
@@ -166,7 +166,7 @@ def _y4m_tag_fields(tag):
 def y4m_tag(chroma_format, bitdepth=8, chroma_loc="center"):
     """the C tag written for pictures of that format, depth and siting"""
     check_format(chroma_format)
-    if not _is_int(bitdepth) or not 8 <= bitdepth <= 16:
+    if not is_int(bitdepth) or not 8 <= bitdepth <= 16:
         raise ValueError(f"bitdepth is 8 or 9..16 (got {bitdepth!r})")
     if bitdepth > 8:
         return f"{chroma_format}p{bitdepth}"
@@ -180,7 +180,7 @@ def _check_rate(frame_rate, what):
         num, den = frame_rate
     except (TypeError, ValueError):
         raise ValueError(f"{what}: a frame rate is (num, den) (got {frame_rate!r})") from None
-    if not _is_int(num) or not _is_int(den) or num <= 0 or den <= 0:
+    if not is_int(num) or not is_int(den) or num <= 0 or den <= 0:
         raise ValueError(f"{what}: a frame rate is two positive integers (got {num!r}:{den!r})")
     return num, den
 
@@ -287,7 +287,7 @@ class PlanarReader:
             bitdepth = 8 if bitdepth is None else bitdepth
             chroma_format = chroma_format or "420"
         check_side(width, height, str(src_file))
-        if not _is_int(bitdepth) or not 8 <= bitdepth <= 16:
+        if not is_int(bitdepth) or not 8 <= bitdepth <= 16:
             raise ValueError(f"bitdepth is 8, or 9..16 for files of 16-bit samples (got {bitdepth!r})")
         self.width, self.height, self.bitdepth = width, height, bitdepth
         self.chroma_format = check_format(chroma_format)
@@ -351,11 +351,6 @@ class PlanarReader:
 
 # ----------------------------------------------------------------------------------------------------- the header file
 def _check_source_record(path, record):
-    if not isinstance(record, dict) or record.get("format_version") != SOURCE_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {SOURCE_FORMAT_VERSION}")
-    if set(record) != set(SOURCE_FIELDS):
-        raise ValueError(f"{path}: fields {sorted(record)}, expected {sorted(SOURCE_FIELDS)}")
     if record["filter"] != FILTER:
         raise ValueError(f"{path}: filter {record['filter']!r}, this decoder knows {FILTER!r}")
     if record["chroma_format"] not in FORMATS or not isinstance(record["chroma_format"], str):
@@ -378,10 +373,7 @@ def write_source_format(bin_folder, chroma_format, chroma_loc, frame_rate=None):
     record = {"format_version": SOURCE_FORMAT_VERSION, "chroma_format": chroma_format, "chroma_loc": chroma_loc,
               "filter": FILTER, "frame_rate": list(frame_rate) if isinstance(frame_rate, tuple) else frame_rate}
     _check_source_record(path, record)
-    with open(path, "w") as f:
-        json.dump(record, f, indent=2, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=2)
 
 
 def read_source_format(bin_folder):
@@ -389,52 +381,39 @@ def read_source_format(bin_folder):
     file, another version or filter, an unknown or missing field, an unknown format or siting, a wrong type, and 4:2:2
     with "center" """
     path = os.path.join(bin_folder, SOURCE_FORMAT)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        return None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a source format file ({e})") from None
-    _check_source_record(path, record)
+    record = read_record(path, "source format file", SOURCE_FORMAT_VERSION, fields=SOURCE_FIELDS,
+                         expected=sorted(SOURCE_FIELDS))
+    if record is not None:
+        _check_source_record(path, record)
     return record
 
 
 # ------------------------------------------------------------------------------------------------------------ encoding
-class _Ingest:
-    def __init__(self, to420, inner, shape):
-        self.to420, self.inner, self.shape = to420, inner, shape      # shape: (height, width) of what comes out
+class SourcePipeline:
+    """The one description of a source's way into the codec that the encoders' bodies take (pmctf_gop.SequenceEncode): an
+    optional step to 4:2:0 (to420: a Converter), an optional step to the coded size (size: a pmctf_scale.CodedSize), format
+    first, size second, and the one hook that applies them (ingest).  source_size: (width, height) of the source; coded:
+    of what enters the codec.  y4m: the source is a .y4m file.  A .y4m or a source that is not 4:2:0 is read by
+    PlanarReader and recorded in source_format.json; a raw 4:2:0 file by YUVReader, with no record of its format.
+    A raw 4:2:0 source without a coded size has no pipeline at all (None)."""
 
-    def __call__(self, frame):
-        if self.to420 is not None:
-            frame = self.to420(frame)
-        return frame if self.inner is None else self.inner(frame)
-
-
-class ChromaFormat:
-    """What the encoders need to code a width x height source of chroma_format, the `scale` object of their bodies (the
-    shape of pmctf_scale.CodedSize): open_reader(), ingest() (the hook read_gop_device applies to every packed picture
-    after upload: the packed picture of the source's format -> 4:2:0 -> the coded size, if one is asked for),
-    write_header() and display_quality() (the CodedSize's; empty without one).  y4m: the source is a .y4m file."""
-
-    def __init__(self, width, height, chroma_format, device, bitdepth=8, chroma_loc=None, coded_size=None, frame_rate=None,
+    def __init__(self, source_size, chroma_format="420", chroma_loc="center", to420=None, size=None, frame_rate=None,
                  y4m=False):
-        check_side(width, height, "source")
-        self.chroma_format = check_format(chroma_format)
-        self.chroma_loc = resolve_loc(chroma_format, chroma_loc)
-        self.source, self.bitdepth, self.y4m = (width, height), bitdepth, y4m
-        self.frame_rate = None if frame_rate is None else _check_rate(frame_rate, "frame_rate")
-        self.size = None if coded_size is None else \
-            pmctf_scale.CodedSize(width, height, coded_size, device, bitdepth, self.chroma_loc)
-        self.coded = (width, height) if self.size is None else self.size.coded
-        self.to420 = None if chroma_format == "420" else \
-            Converter(width, height, chroma_format, "420", device, bitdepth, self.chroma_loc)
+        self.source, self.chroma_format, self.chroma_loc = source_size, chroma_format, chroma_loc
+        self.to420, self.size, self.frame_rate = to420, size, frame_rate
+        self.planar = y4m or chroma_format != "420"
+        self.coded = source_size if size is None else size.coded
 
-    def open_reader(self, src_file, width, height, start_index=0, bitdepth=8):
-        return PlanarReader(src_file, width, height, start_index, bitdepth, self.chroma_format, self.chroma_loc)
+    def open_reader(self, src_file, width, height, bitdepth=8):
+        if self.planar:
+            return PlanarReader(src_file, width, height, 0, bitdepth, self.chroma_format, self.chroma_loc)
+        from pMCTF.utils.yuv_reader import YUVReader
+        return YUVReader(src_file, width, height, start_index=0, bitdepth=bitdepth)
 
     def ingest(self, keep):
-        return _Ingest(self.to420, None if self.size is None else self.size.ingest(keep), self.coded[::-1])
+        """the hook read_gop_device applies to every packed picture after upload; keep=True also keeps the 4:2:0 source
+        pictures for display_quality"""
+        return pmctf_scale._Ingest(self.to420, self.size, keep, self.coded[::-1])
 
     def display_quality(self, rec):
         return [] if self.size is None else self.size.display_quality(rec)
@@ -442,20 +421,23 @@ class ChromaFormat:
     def write_header(self, bin_folder):
         """display_format.json when coded at another size; source_format.json for a .y4m or a source that is not 4:2:0"""
         written = [] if self.size is None else [self.size.write_header(bin_folder)]
-        if self.y4m or self.chroma_format != "420":
+        if self.planar:
             written.append(write_source_format(bin_folder, self.chroma_format, self.chroma_loc, self.frame_rate))
         return written
 
 
-def _source(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, what):
-    """-> None when nothing of this module is asked for (a raw 4:2:0 source: pmctf_scale's function does it), else the
-    ChromaFormat of the source"""
+def _pipeline(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, what, need_rate=False):
+    """-> the SourcePipeline of the source, None where it has none.  A raw 4:2:0 source is pmctf_scale's case.
+    need_rate: a source without a frame rate (all but a .y4m with an F tag) is a ValueError."""
+    no_rate = "fps=None takes the frame rate of a .y4m header; this source has none"
     import pmctf_gop
     if chroma_format is not None:
         check_format(chroma_format)
     y4m = is_y4m(source)
     if not y4m and chroma_format in (None, "420"):
-        return None
+        if need_rate:
+            raise ValueError(no_rate)
+        return pmctf_scale._pipeline(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc or "center", what)
     if kwargs.get("src_format", "yuv") != "yuv":
         raise ValueError(f"{what}: chroma_format and .y4m sources are planar files (src_format='yuv')")
     bitdepth = pmctf_gop.check_bitdepth(kwargs.get("bitdepth", 8))
@@ -469,9 +451,16 @@ def _source(source, width, height, device, kwargs, coded_size, chroma_format, ch
         chroma_format, rate = head["chroma_format"], head["frame_rate"]
         if chroma_loc is None:
             chroma_loc = head["chroma_loc"]
-    resolve_loc(chroma_format, chroma_loc)
+    chroma_loc = resolve_loc(chroma_format, chroma_loc)
     pmctf_gop._need_gpu(device, f"{what}(chroma_format={chroma_format!r}, source={os.path.basename(os.fspath(source))!r})")
-    return ChromaFormat(width, height, chroma_format, device, bitdepth, chroma_loc, coded_size, rate, y4m)
+    check_side(width, height, "source")
+    if rate is not None:
+        rate = _check_rate(rate, "frame_rate")
+    size = None if coded_size is None else pmctf_scale.CodedSize(width, height, coded_size, device, bitdepth, chroma_loc)
+    to420 = None if chroma_format == "420" else Converter(width, height, chroma_format, "420", device, bitdepth, chroma_loc)
+    if need_rate and rate is None:
+        raise ValueError(no_rate)
+    return SourcePipeline((width, height), chroma_format, chroma_loc, to420, size, rate, y4m)
 
 
 def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device, *, coded_size=None,
@@ -483,14 +472,11 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     tables are those of coding the converted pictures.  chroma_loc=None: the header's siting, else the format's default
     ("left" for 4:2:2, "center" otherwise).  With keep_gops=True the folder gets source_format.json when the source is a
     .y4m or not 4:2:0.  The result has "display_quality" (empty without a coded_size).
-    A raw 4:2:0 .yuv with chroma_format=None: pmctf_scale.encode_sequence itself, same files, no new header."""
+    A raw 4:2:0 .yuv with chroma_format=None: what pmctf_scale.encode_sequence does, same files, no new header."""
     import pmctf_gop
-    fmt = _source(yuv_path, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence")
-    if fmt is None:
-        return pmctf_scale.encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                                           coded_size=coded_size, chroma_loc=chroma_loc or "center", **kwargs)
-    return pmctf_gop._encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                                      scale=fmt, **kwargs)
+    pipeline = _pipeline(yuv_path, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence")
+    return pmctf_gop._encode_equal_gops(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
+                                        pipeline=pipeline, **kwargs)
 
 
 def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device, *,
@@ -498,12 +484,9 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     """pmctf_scale.encode_sequence_gops with chroma_format / chroma_loc as encode_sequence above has them; the scene-cut
     pass looks at the converted pictures."""
     import pmctf_seq
-    fmt = _source(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence_gops")
-    if fmt is None:
-        return pmctf_scale.encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
-                                                coded_size=coded_size, chroma_loc=chroma_loc or "center", **kwargs)
-    return pmctf_seq._encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
-                                           scale=fmt, **kwargs)
+    pipeline = _pipeline(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence_gops")
+    return pmctf_seq._encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
+                                      pipeline=pipeline, **kwargs)
 
 
 def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device, *,
@@ -511,16 +494,12 @@ def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitra
     """pmctf_scale.encode_sequence_rate with chroma_format / chroma_loc as encode_sequence above has them; fps=None takes
     the frame rate of the .y4m header (ValueError when there is none)."""
     import pmctf_rate
-    fmt = _source(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence_rate")
+    pipeline = _pipeline(source, width, height, device, kwargs, coded_size, chroma_format, chroma_loc, "encode_sequence_rate",
+                         need_rate=fps is None)
     if fps is None:
-        if fmt is None or fmt.frame_rate is None:
-            raise ValueError("fps=None takes the frame rate of a .y4m header; this source has none")
-        fps = fmt.frame_rate
-    if fmt is None:
-        return pmctf_scale.encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder,
-                                                device, coded_size=coded_size, chroma_loc=chroma_loc or "center", **kwargs)
-    return pmctf_rate._encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder,
-                                            device, scale=fmt, **kwargs)
+        fps = pipeline.frame_rate
+    return pmctf_rate._encode_at_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device,
+                                      pipeline=pipeline, **kwargs)
 
 
 # ------------------------------------------------------------------------------------------------------------ decoding
@@ -531,6 +510,7 @@ class OutputFormat:
     def __init__(self, record, y4m, coded, display, device, bitdepth):
         self.display, self.coded, self.bitdepth = display, coded, bitdepth
         self.size = coded if display is None else display.size
+        self.shape = self.size[::-1]
         self.chroma_format = "420" if record is None else record["chroma_format"]
         self.chroma_loc = record["chroma_loc"] if record is not None else \
             (display.up.chroma_loc if display is not None else "center")
@@ -552,6 +532,13 @@ class OutputFormat:
         if self.from420 is not None:
             frames = [self.from420(f) for f in frames]
         return [unpack_frame(f, H, W, self.chroma_format) for f in frames]
+
+    def rgb8(self, frames_rec):
+        """the PNGs' pictures: those of the 4:2:0 pictures, at the display size if there is one"""
+        if self.display is not None:
+            return self.display.rgb8(frames_rec)
+        import pmctf_gop
+        return pmctf_gop.frames_to_rgb8(frames_rec, self.coded[1], self.coded[0])
 
 
 def output_format(bin_folder, yuv_out, coded_width, coded_height, display, device, bitdepth=8, coded_format_output=False):
@@ -576,13 +563,15 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     recorded frame rate, 25:1 when none is recorded, Ip A0:0) and FRAME markers; any other path raw planes.  png_out takes
     its RGB from the 4:2:0 pictures; the hashes are those of the coded 4:2:0 pictures and are verified before."""
     import pmctf_gop
-    return pmctf_gop._decode_sequence(codec, bin_folder, yuv_out, device, png_out, verify, coded_size_output,
-                                      coded_format_output)
+    return pmctf_gop.decode_sequence_with(pmctf_gop.FullDecode(), codec, bin_folder, yuv_out, device, png_out, verify,
+                                          coded_size_output=coded_size_output, coded_format_output=coded_format_output)
 
 
 def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False,
                           coded_size_output=False, coded_format_output=False):
     """pmctf_scale.decode_sequence_layer with coded_format_output as decode_sequence_checked above has it"""
+    import pmctf_gop
     import pmctf_layers
-    return pmctf_layers._decode_sequence_layer(codec, bin_folder, yuv_out, level, device, png_out, verify, motion_fill,
-                                               coded_size_output, coded_format_output)
+    return pmctf_gop.decode_sequence_with(pmctf_layers.LayerDecode(level, motion_fill), codec, bin_folder, yuv_out, device,
+                                          png_out, verify, coded_size_output=coded_size_output,
+                                          coded_format_output=coded_format_output)

@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from pmctf_records import is_int, read_record, write_record
+
 
 def psnr(a, b):
     """test_pMCTF_flex.py:81-84"""
@@ -361,9 +363,9 @@ def read_gop_device(reader, gop, device, psize=128):
     picture costs one copy of its bytes to the device and one launch (pmctf_yuv420_u8_to_planes_f32: conversion, padding
     and the un-padded originals); from a PNGReader the RGB bytes are copied and converted to 4:2:0 first
     (pmctf_rgb8_to_yuv420_u8).  A YUVReader of 16-bit samples goes through pmctf_yuv420_u16_to_planes_f32 the same way.
-    A reader with a `resample` attribute (pmctf_scale.CodedSize.ingest: a sequence coded at another size than its source's)
-    has every packed picture resampled on the device before the planes are made; the triple is then that of a source of
-    resample.shape."""
+    A reader with a `resample` attribute (pmctf_chroma.SourcePipeline.ingest: a source in another chroma format, or coded at
+    another size than its own) has every packed picture converted on the device before the planes are made; the triple is
+    then that of a 4:2:0 source of resample.shape."""
     import numpy as np
     from pMCTF.hip import ops
     _need_gpu(device, "read_gop_device")
@@ -470,107 +472,153 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     decoded_frame_path are refused (ValueError), picture_hash is "u16" or "f32".  With keep_gops=True bin_folder also gets
     picture_format.json (write_picture_format), which tells decode_sequence the depth.
     pmctf_scale.encode_sequence(..., coded_size=(W, H)) is this function for a sequence coded at another size than its
-    source's (a pmctf_scale.CodedSize handed to the shared body): the pictures are resampled on the device after upload
+    source's (the body with a pmctf_chroma.SourcePipeline): the pictures are resampled on the device after upload
     (read_gop_device, whatever `ingest` says) and everything below sees a source of the coded size, sequence.json included;
     with keep_gops=True bin_folder also gets display_format.json, and the result gains "display_quality".
     Returns {"log": record, "json": its text, "bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types", "lines"} (+ "msssim")."""
-    return _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device, skip_decoding, psize,
-                            src_format, ingest, decoded_frame_path, picture_hash, bitdepth, keep_gops, msssim)
+    return _encode_equal_gops(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
+                              skip_decoding=skip_decoding, psize=psize, src_format=src_format, ingest=ingest,
+                              decoded_frame_path=decoded_frame_path, picture_hash=picture_hash, bitdepth=bitdepth,
+                              keep_gops=keep_gops, msssim=msssim)
 
 
-def _encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                     skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
-                     picture_hash=None, bitdepth=8, keep_gops=False, msssim=False, scale=None):
-    """encode_sequence's body; scale: a pmctf_scale.CodedSize (pmctf_scale.encode_sequence), a pmctf_chroma.ChromaFormat
-    (pmctf_chroma.encode_sequence: it also opens the reader of its source) or None"""
-    import io
+class SequenceEncode:
+    """What encode_sequence's loop and pmctf_seq's GOP-list loop share: encode_sequence's keywords after `device` with their
+    refusals (raised here, in this order, before the codec or the source is touched), the reader of the source, the tables
+    of the GOPs coded so far, the sidecar files of the folder and the result.
+    pipeline: the pmctf_chroma.SourcePipeline of a source that is converted or resampled on its way into the codec, None
+    for one that enters as it is: then a .yuv is read by YUVReader and, with ingest="host", through read_gop."""
+
+    def __init__(self, pipeline=None, skip_decoding=True, psize=128, src_format="yuv", ingest="host", decoded_frame_path=None,
+                 picture_hash=None, bitdepth=8, keep_gops=False, msssim=False):
+        if picture_hash is not None and picture_hash not in HASH_LEVELS:
+            raise ValueError(f"picture_hash is None or one of {HASH_LEVELS} (got {picture_hash!r})")
+        if picture_hash is not None and not keep_gops:
+            raise ValueError("picture_hash needs keep_gops=True: the hashes belong to a folder decode_sequence can read")
+        bitdepth = check_bitdepth(bitdepth)
+        if picture_hash is not None:
+            check_hash_level(picture_hash, bitdepth)
+        if bitdepth > 8:
+            if src_format == "png":
+                raise ValueError(f"bitdepth {bitdepth}: a source above 8 bits is a .yuv file (src_format='yuv'), PNG input is 8-bit")
+            if msssim:
+                raise ValueError(f"bitdepth {bitdepth}: MS-SSIM and RGB-PSNR are defined on 8-bit RGB pictures (msssim=False)")
+            if decoded_frame_path is not None:
+                raise ValueError(f"bitdepth {bitdepth}: decoded_frame_path writes 8-bit PNGs; decode the folder to a .yuv instead")
+        self.pipeline, self.skip_decoding, self.psize, self.keep_gops = pipeline, skip_decoding, psize, keep_gops
+        self.src_format, self.ingest, self.bitdepth = src_format, ingest, bitdepth
+        self.decoded_frame_path, self.picture_hash, self.msssim = decoded_frame_path, picture_hash, msssim
+        self.on_device = src_format == "png" or ingest == "device" or pipeline is not None
+        self.tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
+        self.lines, self.ssims, self.hashes, self.display = [], [], [], []
+        self.pairs = 0
+        self.seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
+
+    def check_source_kind(self):
+        if self.src_format not in ("yuv", "png") or self.ingest not in ("host", "device"):
+            raise ValueError(f"src_format is 'yuv' or 'png' and ingest 'host' or 'device' (got {self.src_format!r}, "
+                             f"{self.ingest!r})")
+
+    def open_reader(self, source, width, height, frame_num, keep=False):
+        """a fresh reader of the source; with a pipeline its pictures are converted on the device after upload
+        (read_gop_device), and keep=True keeps them for the pipeline's display_quality"""
+        if self.src_format == "png":
+            reader = PNGReader(source)
+            if (reader.width, reader.height) != (width, height):
+                raise ValueError(f"the pictures are {reader.width}x{reader.height}, not {width}x{height}")
+            if len(reader) < frame_num:
+                raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
+        elif self.pipeline is not None:
+            reader = self.pipeline.open_reader(source, width, height, self.bitdepth)
+        else:
+            from pMCTF.utils.yuv_reader import YUVReader
+            reader = YUVReader(source, width, height, start_index=0, bitdepth=self.bitdepth)
+        if self.pipeline is not None:
+            reader.resample = self.pipeline.ingest(keep)
+        return reader
+
+    def read_gop(self, reader, size, device, psize):
+        return (read_gop_device if self.on_device else read_gop)(reader, size, device, psize)
+
+    def add_pairs(self, enc):
+        """the times and the report lines of the pairs of one encode_gop result"""
+        for r in enc["results"]:
+            self.pairs += 1
+            for k in self.seconds:
+                self.seconds[k] += r[k]
+        self.lines += enc["log"]
+
+    def add_gop(self, rec, orig, h, w, bits, bits_mv, first_frame):
+        """one reconstructed GOP: report_gop, and the pipeline's display quality"""
+        report_gop(rec, orig, h, w, bits, bits_mv, first_frame, self.tables, self.ssims, self.hashes,
+                   picture_hash=self.picture_hash, bitdepth=self.bitdepth, decoded_frame_path=self.decoded_frame_path,
+                   msssim=self.msssim)
+        if self.pipeline is not None:
+            self.display += self.pipeline.display_quality(rec)
+
+    def write_sidecars(self, bin_folder):
+        """what a folder holds beside its header: the picture hashes, the picture format, the pipeline's records"""
+        if self.picture_hash is not None:
+            write_picture_hashes(bin_folder, self.picture_hash, self.hashes)
+        if self.bitdepth > 8:
+            write_picture_format(bin_folder, self.bitdepth)
+        if self.pipeline is not None:
+            self.pipeline.write_header(bin_folder)
+
+    def average_lines(self):
+        for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
+            self.lines.append(f"{label} {self.pairs} P frames, average {self.seconds[k] / self.pairs * 1000:.0f} ms.")
+
+    def result(self, frame_num, width, height, t0, **extra):
+        import io
+        import time
+        from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
+        tables = self.tables
+        record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
+                                   tables["psnr_rgb"], self.ssims if self.msssim else [0] * frame_num, height * width,
+                                   time.time() - t0)
+        text = io.StringIO()
+        dump_json(record, text, float_digits=6, indent=2)
+        out = dict(tables, log=record, json=text.getvalue(), lines=self.lines, **extra)
+        if self.msssim:
+            out["msssim"] = self.ssims
+        if self.picture_hash is not None:
+            out["picture_hashes"] = self.hashes
+        if self.pipeline is not None:
+            out["display_quality"] = self.display
+        return out
+
+
+def _encode_equal_gops(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device, *, pipeline=None, **options):
+    """encode_sequence's body; options: its keywords after `device` (SequenceEncode)"""
     import time
-    if picture_hash is not None and picture_hash not in HASH_LEVELS:
-        raise ValueError(f"picture_hash is None or one of {HASH_LEVELS} (got {picture_hash!r})")
-    if picture_hash is not None and not keep_gops:
-        raise ValueError("picture_hash needs keep_gops=True: the hashes belong to a folder decode_sequence can read")
-    bitdepth = check_bitdepth(bitdepth)
-    if picture_hash is not None:
-        check_hash_level(picture_hash, bitdepth)
-    if bitdepth > 8:
-        if src_format == "png":
-            raise ValueError(f"bitdepth {bitdepth}: a source above 8 bits is a .yuv file (src_format='yuv'), PNG input is 8-bit")
-        if msssim:
-            raise ValueError(f"bitdepth {bitdepth}: MS-SSIM and RGB-PSNR are defined on 8-bit RGB pictures (msssim=False)")
-        if decoded_frame_path is not None:
-            raise ValueError(f"bitdepth {bitdepth}: decoded_frame_path writes 8-bit PNGs; decode the folder to a .yuv instead")
-    from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
-    from pMCTF.utils.yuv_reader import YUVReader
+    e = SequenceEncode(pipeline, **options)
     assert frame_num % gop == 0
-    if src_format not in ("yuv", "png") or ingest not in ("host", "device"):
-        raise ValueError(f"src_format is 'yuv' or 'png' and ingest 'host' or 'device' (got {src_format!r}, {ingest!r})")
-    on_device = src_format == "png" or ingest == "device" or scale is not None
-    if on_device:
-        _need_gpu(device, f"encode_sequence(src_format={src_format!r}, ingest={ingest!r})")
-    if src_format == "png":
-        reader = PNGReader(yuv_path)
-        if (reader.width, reader.height) != (width, height):
-            raise ValueError(f"the pictures are {reader.width}x{reader.height}, not {width}x{height}")
-        if len(reader) < frame_num:
-            raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
-    else:
-        reader = (getattr(scale, "open_reader", None) or YUVReader)(yuv_path, width, height, start_index=0,
-                                                                    bitdepth=bitdepth)
-    display = []
-    if scale is not None:
-        reader.resample = scale.ingest(keep=True)
-        width, height = scale.coded
-    tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
-    lines = []
-    ssims = []
-    hashes = []
-    pairs = 0
-    seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
+    e.check_source_kind()
+    if e.on_device:
+        _need_gpu(device, f"encode_sequence(src_format={e.src_format!r}, ingest={e.ingest!r})")
+    reader = e.open_reader(yuv_path, width, height, frame_num, keep=True)
+    if pipeline is not None:
+        width, height = pipeline.coded
     t0 = time.time()
     with torch.no_grad():
         for k in range(frame_num // gop):
-            padded, orig, (h, w) = (read_gop_device if on_device else read_gop)(reader, gop, device, psize)
-            first_frame = k * gop
+            padded, orig, (h, w) = e.read_gop(reader, gop, device, e.psize)
             folder = bin_folder
-            if keep_gops:
+            if e.keep_gops:
                 folder = os.path.join(bin_folder, gop_folder(k))
                 os.makedirs(folder, exist_ok=True)
-            enc = encode_gop(codec, padded, h, w, q_index, folder, skip_decoding=skip_decoding, psize=psize)
-            for r in enc["results"]:
-                pairs += 1
-                for k in seconds:
-                    seconds[k] += r[k]
-            lines += enc["log"]
-            rec = decode_gop(codec, enc["frames_coded"])
-            report_gop(rec, orig, h, w, enc["bits"], enc["bits_mv"], first_frame, tables, ssims, hashes,
-                       picture_hash=picture_hash, bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
-            if scale is not None:
-                display += scale.display_quality(rec)
+            enc = encode_gop(codec, padded, h, w, q_index, folder, skip_decoding=e.skip_decoding, psize=e.psize)
+            e.add_pairs(enc)
+            e.add_gop(decode_gop(codec, enc["frames_coded"]), orig, h, w, enc["bits"], enc["bits_mv"], k * gop)
     reader.close()
-    if keep_gops:
+    if e.keep_gops:
         write_sequence_header(bin_folder, width=width, height=height, frame_num=frame_num, gop=gop, q_index=q_index,
-                              psize=psize, me_downsample=1, ll_order="plane" if skip_decoding else "position",
+                              psize=e.psize, me_downsample=1, ll_order="plane" if e.skip_decoding else "position",
                               **codec_header_fields(codec))
-        if picture_hash is not None:
-            write_picture_hashes(bin_folder, picture_hash, hashes)
-        if bitdepth > 8:
-            write_picture_format(bin_folder, bitdepth)
-        if scale is not None:
-            scale.write_header(bin_folder)
-    for k, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
-        lines.append(f"{label} {pairs} P frames, average {seconds[k] / pairs * 1000:.0f} ms.")
-    record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
-                               tables["psnr_rgb"], ssims if msssim else [0] * frame_num, height * width, time.time() - t0)
-    text = io.StringIO()
-    dump_json(record, text, float_digits=6, indent=2)
-    out = dict(tables, log=record, json=text.getvalue(), lines=lines)
-    if msssim:
-        out["msssim"] = ssims
-    if picture_hash is not None:
-        out["picture_hashes"] = hashes
-    if scale is not None:
-        out["display_quality"] = display
-    return out
+        e.write_sidecars(bin_folder)
+    e.average_lines()
+    return e.result(frame_num, width, height, t0)
 
 
 def quality_line(idx, q, bpp=None, seconds=None):
@@ -693,7 +741,6 @@ def codec_header_fields(codec):
 
 def write_sequence_header(bin_folder, **fields):
     """bin_folder/sequence.json: format version + SEQUENCE_FIELDS (all required, nothing else accepted)"""
-    import json
     if set(fields) != set(SEQUENCE_FIELDS):
         raise ValueError(f"sequence header fields: missing {sorted(set(SEQUENCE_FIELDS) - set(fields))}, "
                          f"unknown {sorted(set(fields) - set(SEQUENCE_FIELDS))}")
@@ -701,26 +748,13 @@ def write_sequence_header(bin_folder, **fields):
         raise ValueError(f"ll_order must be one of {LL_ORDERS}")
     record = {"format_version": SEQUENCE_FORMAT_VERSION}
     record.update({k: fields[k] if k in ("ll_order", "precision") else int(fields[k]) for k in SEQUENCE_FIELDS})
-    path = os.path.join(bin_folder, SEQUENCE_HEADER)
-    with open(path, "w") as f:
-        json.dump(record, f, indent=2, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(os.path.join(bin_folder, SEQUENCE_HEADER), record, indent=2)
 
 
 def read_sequence_header(bin_folder):
-    import json
     path = os.path.join(bin_folder, SEQUENCE_HEADER)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        raise ValueError(f"{path}: missing (not a folder written with encode_sequence(keep_gops=True))") from None
-    except json.JSONDecodeError as e:
-        raise ValueError(f"{path}: not a sequence header ({e})") from None
-    if not isinstance(record, dict) or record.get("format_version") != SEQUENCE_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {SEQUENCE_FORMAT_VERSION}")
+    record = read_record(path, "sequence header", SEQUENCE_FORMAT_VERSION,
+                         missing="not a folder written with encode_sequence(keep_gops=True)")
     missing = [k for k in SEQUENCE_FIELDS if k not in record]
     if missing:
         raise ValueError(f"{path}: fields {missing} missing")
@@ -747,35 +781,22 @@ PICTURE_FORMAT_VERSION = 1
 def write_picture_format(bin_folder, bitdepth):
     """bin_folder/picture_format.json: {"format_version", "bitdepth"}, the depth 9..16 of the source's 16-bit samples.
     Written beside sequence.json only for a source above 8 bits; the bitstream files and sequence.json do not know it."""
-    import json
     path = os.path.join(bin_folder, PICTURE_FORMAT)
     try:
         bitdepth = check_bitdepth(bitdepth, above8=True)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from None
-    with open(path, "w") as f:
-        json.dump({"format_version": PICTURE_FORMAT_VERSION, "bitdepth": bitdepth}, f, indent=2, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, {"format_version": PICTURE_FORMAT_VERSION, "bitdepth": bitdepth}, indent=2)
 
 
 def read_picture_format(bin_folder):
     """-> the bit depth of the folder's pictures: 8 when there is no picture_format.json, else the 9..16 it holds;
     ValueError naming the path for a malformed file, another version, an unknown field or another depth"""
-    import json
     path = os.path.join(bin_folder, PICTURE_FORMAT)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
+    record = read_record(path, "picture format file", PICTURE_FORMAT_VERSION, fields=("bitdepth",),
+                         expected="format_version and bitdepth")
+    if record is None:
         return 8
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a picture format file ({e})") from None
-    if not isinstance(record, dict) or record.get("format_version") != PICTURE_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {PICTURE_FORMAT_VERSION}")
-    if set(record) != {"format_version", "bitdepth"}:
-        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version and bitdepth")
     try:
         return check_bitdepth(record["bitdepth"], above8=True)
     except ValueError as e:
@@ -1012,40 +1033,25 @@ def _check_hash_records(path, level, frames, frame_num=None):
         if not isinstance(rec, dict) or set(rec) != set(HASH_KEYS[level]):
             raise ValueError(f"{path}: frame {i}: a record of level {level!r} holds exactly {HASH_KEYS[level]}")
         for k, v in rec.items():
-            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 0xffffffff:
+            if not is_int(v) or not 0 <= v <= 0xffffffff:
                 raise ValueError(f"{path}: frame {i}: {k} is not a 32-bit value ({v!r})")
 
 
 def write_picture_hashes(bin_folder, level, frames):
     """bin_folder/picture_hashes.json: format version, level and one picture_hashes record per frame in display order"""
-    import json
     path = os.path.join(bin_folder, PICTURE_HASHES)
     _check_hash_records(path, level, frames)
     record = {"format_version": PICTURE_HASH_FORMAT_VERSION, "level": level,
               "frames": [{k: int(rec[k]) for k in HASH_KEYS[level]} for rec in frames]}
-    with open(path, "w") as f:
-        json.dump(record, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=1)
 
 
 def read_picture_hashes(bin_folder, frame_num):
     """-> {"format_version", "level", "frames"}; ValueError naming the path for a missing or malformed file, another
     version, an unknown level or a frame list that does not have frame_num well-formed records"""
-    import json
     path = os.path.join(bin_folder, PICTURE_HASHES)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        raise ValueError(f"{path}: missing (the sequence was coded without picture_hash)") from None
-    except json.JSONDecodeError as e:
-        raise ValueError(f"{path}: not a picture hash file ({e})") from None
-    if not isinstance(record, dict) or record.get("format_version") != PICTURE_HASH_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {PICTURE_HASH_FORMAT_VERSION}")
-    if set(record) != {"format_version", "level", "frames"}:
-        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version, level and frames")
+    record = read_record(path, "picture hash file", PICTURE_HASH_FORMAT_VERSION, fields=("level", "frames"),
+                         missing="the sequence was coded without picture_hash", expected="format_version, level and frames")
     _check_hash_records(path, record["level"], record["frames"], frame_num)
     return record
 
@@ -1132,21 +1138,86 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     are those of the 4:2:0 pictures either way.
     Returns decode_sequence's dict: "verified" counts the pictures checked, "hash_mismatches" lists {"gop", "folder",
     "frame", "plane", "decoded", "recorded"}; "frames" holds the written sizes."""
-    return _decode_sequence(codec, bin_folder, yuv_out, device, png_out, verify)
+    return decode_sequence_with(FullDecode(), codec, bin_folder, yuv_out, device, png_out, verify)
 
 
-def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", coded_size_output=False,
-                     coded_format_output=False):
-    """decode_sequence_checked's body; coded_size_output: pmctf_scale.decode_sequence_checked; coded_format_output:
-    pmctf_chroma.decode_sequence_checked (a folder with a source_format.json is written in its source's chroma format, a
-    yuv_out ending in .y4m as a Y4M file)"""
+class PlainSink:
+    """The picture sink of a folder with no display_format.json and no source_format.json in force and no .y4m to write: the
+    pictures as they were coded, through frames_to_u8 / frames_to_u16 and frames_to_rgb8, and nothing else of the device.
+    pmctf_scale.DisplaySize and pmctf_chroma.OutputFormat are the other two sinks (picture_sink)."""
+    stream_header = frame_marker = b""
+
+    def __init__(self, height, width, bitdepth):
+        self.shape, self.bitdepth = (height, width), bitdepth             # shape: of every written picture
+
+    def pictures(self, frames_rec):
+        if self.bitdepth > 8:
+            return frames_to_u16(frames_rec, *self.shape, self.bitdepth)
+        return frames_to_u8(frames_rec, *self.shape)
+
+    def rgb8(self, frames_rec):
+        return frames_to_rgb8(frames_rec, *self.shape)
+
+
+def picture_sink(bin_folder, yuv_out, width, height, device, bitdepth, coded_size_output=False, coded_format_output=False):
+    """-> what turns the reconstructed pictures of a decode of bin_folder into bytes, built once per decode:
+    .stream_header (written once), .frame_marker (before every picture), .pictures(frames) -> [(Y, Cb, Cr)] integer arrays,
+    .rgb8(frames) -> [(h, w, 3) uint8 arrays] for the PNGs, .shape: (height, width) of what is written.
+    display_format.json and source_format.json are validated even where coded_size_output / coded_format_output switch
+    their effect off."""
+    import pmctf_chroma
+    import pmctf_scale
+    display = pmctf_scale.display_size(bin_folder, width, height, device, bitdepth, coded_size_output)
+    fmt = pmctf_chroma.output_format(bin_folder, yuv_out, width, height, display, device, bitdepth, coded_format_output)
+    if fmt is not None:
+        return fmt
+    return display if display is not None else PlainSink(height, width, bitdepth)
+
+
+class FullDecode:
+    """What decode_sequence_with is parameterised by, here for every picture of the sequence (decode_sequence_checked):
+    how one GOP is decoded and which recorded hashes apply to its pictures.  pmctf_layers.LayerDecode is the one for a
+    temporal level."""
+    hash_level = None                                                     # None: nothing to check the pictures against
+
+    def refuse(self, verify):
+        """refusals of its own, raised between that of `verify` and that of having nothing to write"""
+
+    def check_folder(self, bin_folder):
+        """refusals that need the folder, raised once its header is read"""
+
+    def open(self, bin_folder, header, gops, verify):
+        if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
+            full = read_picture_hashes(bin_folder, header["frame_num"])
+            self.frames, self.hash_level = full["frames"], full["level"]
+
+    def decode_gop(self, codec, folder, size, h, w, q_index, psize, me_downsample, ll_order):
+        """-> (the GOP's pictures, their offsets within the GOP, the bytes read or None where they are not counted)"""
+        out = decode_gop_files(codec, folder, size, h, w, q_index, psize=psize, me_downsample=me_downsample, ll_order=ll_order)
+        return out["frames"], range(size), None
+
+    def recorded(self, first, size, at, n):
+        """-> the records of the n pictures decoded from the GOP of `size` pictures at `first`, `at` pictures written so far"""
+        return self.frames[first:first + size]
+
+    def result(self, times, nbytes):
+        return {}
+
+
+def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", *,
+                         coded_size_output=False, coded_format_output=False):
+    """The one sequence decoder: decode_sequence_checked (mode: a FullDecode) and pmctf_layers.decode_sequence_layer (a
+    LayerDecode), and under the output flags pmctf_scale's and pmctf_chroma's forms of both.  A FullDecode and a LayerDecode
+    of level 0 without motion_fill decode the same pictures in the same order, so they write the same bytes."""
     import contextlib
     import time
     if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
         raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
+    mode.refuse(verify)
     if yuv_out is None and png_out is None:
         raise ValueError("nothing to write: give yuv_out, png_out or both")
     header, gops = sequence_layout(bin_folder)
+    mode.check_folder(bin_folder)
     bitdepth = read_picture_format(bin_folder)
     if bitdepth > 8 and png_out is not None:
         raise ValueError(f"{os.path.join(bin_folder, PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
@@ -1155,49 +1226,41 @@ def _decode_sequence(codec, bin_folder, yuv_out, device=None, png_out=None, veri
     dev = codec.engine().dev
     if device is not None and torch.device(device).type != dev.type:
         raise ValueError(f"the codec lives on {dev}, not on {device}")
-    recorded = None
-    if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
-        recorded = read_picture_hashes(bin_folder, header["frame_num"])
+    mode.open(bin_folder, header, gops, verify)
     h, w = header["height"], header["width"]
-    import pmctf_scale
-    display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
-    out_shape = (h, w) if display is None else display.size[::-1]
-    import pmctf_chroma
-    fmt = pmctf_chroma.output_format(bin_folder, yuv_out, w, h, display, dev, bitdepth, coded_format_output)
+    sink = picture_sink(bin_folder, yuv_out, w, h, dev, bitdepth, coded_size_output, coded_format_output)
     q_indexes = gop_q_indexes(header, len(gops))
-    shapes, seconds, mismatches, verified = [], [], [], 0
+    shapes, seconds, mismatches, times = [], [], [], []
+    verified = nbytes = 0
     with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
-        if f is not None and fmt is not None:
-            f.write(fmt.stream_header)
+        if f is not None:
+            f.write(sink.stream_header)
         for k, (first, size, psize, me_downsample) in enumerate(gops):
             t0 = time.time()
             folder = os.path.join(bin_folder, gop_folder(k))
-            out = decode_gop_files(codec, folder, size, h, w, q_indexes[k], psize=psize, me_downsample=me_downsample,
-                                   ll_order=header["ll_order"])
-            if recorded is not None:
-                bad = compare_hash_records(picture_hashes(out["frames"], h, w, recorded["level"], bitdepth),
-                                           recorded["frames"][first:first + size], first, gop=k, folder=folder)
+            frames, offsets, nread = mode.decode_gop(codec, folder, size, h, w, q_indexes[k], psize, me_downsample,
+                                                     header["ll_order"])
+            source = [first + t for t in offsets]                         # the source index of every decoded picture
+            if mode.hash_level is not None:
+                got = picture_hashes(frames, h, w, mode.hash_level, bitdepth)
+                bad = []
+                for t, a, b in zip(source, got, mode.recorded(first, size, len(times), len(source))):
+                    bad += compare_hash_records([a], [b], t, gop=k, folder=folder)   # per source frame
                 if bad and verify != "report":
                     raise PictureHashMismatch(bad[0])
                 mismatches += bad
-                verified += size
+                verified += len(source)
             if f is not None:
-                if fmt is not None:
-                    pictures = fmt.pictures(out["frames"])
-                elif display is not None:
-                    pictures = display.pictures(out["frames"])
-                else:
-                    pictures = frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
-                        frames_to_u8(out["frames"], h, w)
-                for planes in pictures:
-                    if fmt is not None:
-                        f.write(fmt.frame_marker)
+                for planes in sink.pictures(frames):
+                    f.write(sink.frame_marker)
                     for p in planes:
                         f.write(p.tobytes(order="C"))
             if png_out is not None:
-                write_pngs(png_out, first, frames_to_rgb8(out["frames"], h, w) if display is None else
-                           display.rgb8(out["frames"]))
-            shapes += [out_shape] * size
+                for t, rgb in zip(source, sink.rgb8(frames)):             # PNGs are named by source index
+                    write_pngs(png_out, t, [rgb])
+            times += source
+            nbytes += nread or 0
+            shapes += [sink.shape] * len(source)
             seconds.append(time.time() - t0)
-    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
-            "bitdepth": bitdepth}
+    return dict({"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
+                 "bitdepth": bitdepth}, **mode.result(times, nbytes))

@@ -15,10 +15,10 @@ Level k >= 0; a GOP of size = 2^S pictures; kk = min(k, S): a GOP shallower than
 motion_fill=True is the other classical use of the same picture files: the motion of the left-out stages is read as
 well, their high-band pictures are taken as zero and the whole synthesis runs, which gives every picture of the GOP.
 The plan, the hash record and extract_layer need no GPU; the decoders have no CPU path."""
-import json
 import os
 
 import pmctf_gop
+from pmctf_records import is_int, read_record, write_record
 
 LAYER_HASHES = "layer_hashes.json"
 LAYER_HASH_FORMAT_VERSION = 1
@@ -27,20 +27,16 @@ LAYER_EXTRACT_VERSION = 1
 L_FILES = ("0_main.bin", "0_C_main.bin")
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def check_level(level):
     """the temporal level as given: an integer >= 0; ValueError otherwise"""
-    if not _is_int(level) or level < 0:
+    if not is_int(level) or level < 0:
         raise ValueError(f"level is an integer, 0 or more (got {level!r})")
     return level
 
 
 def gop_stages(gop):
     """S of a GOP of 2^S pictures (0 for a lone picture); ValueError for a size that is not a power of two"""
-    if not _is_int(gop) or gop < 1 or gop & (gop - 1):
+    if not is_int(gop) or gop < 1 or gop & (gop - 1):
         raise ValueError(f"the GOP length must be a power of two (got {gop!r})")
     return gop.bit_length() - 1
 
@@ -239,13 +235,7 @@ def _layer_path(bin_folder):
 
 
 def _check_layer_record(path, record, gops):
-    """the fields of a layer hash record against the folder's layout (see read_layer_hashes)"""
-    if not isinstance(record, dict) or record.get("format_version") != LAYER_HASH_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {LAYER_HASH_FORMAT_VERSION}")
-    want = {"format_version", "level", "layers"}
-    if set(record) != want:
-        raise ValueError(f"{path}: fields missing {sorted(want - set(record))}, unknown {sorted(set(record) - want)}")
+    """what a layer hash record says against the folder's layout (see read_layer_hashes)"""
     level, layers = record["level"], record["layers"]
     if level not in pmctf_gop.HASH_LEVELS:
         raise ValueError(f"{path}: level {level!r}, this decoder knows {pmctf_gop.HASH_LEVELS}")
@@ -264,7 +254,7 @@ def _check_layer_record(path, record, gops):
             raise ValueError(f"{path}: layer {k}: source indices {[r['index'] for r in recs]}, the layout gives {times}")
         for r in recs:
             for key, v in r.items():
-                if key != "index" and (not _is_int(v) or not 0 <= v <= 0xffffffff):
+                if key != "index" and (not is_int(v) or not 0 <= v <= 0xffffffff):
                     raise ValueError(f"{path}: layer {k}: picture {r['index']}: {key} is not a 32-bit value ({v!r})")
 
 
@@ -275,13 +265,8 @@ def read_layer_hashes(bin_folder):
     folder's layout."""
     path = _layer_path(bin_folder)
     _, gops = pmctf_gop.sequence_layout(bin_folder)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        raise ValueError(f"{path}: missing (write_layer_hashes was not run on the folder)") from None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a layer hash file ({e})") from None
+    record = read_record(path, "layer hash file", LAYER_HASH_FORMAT_VERSION, fields=("level", "layers"),
+                         missing="write_layer_hashes was not run on the folder")
     _check_layer_record(path, record, gops)
     return record
 
@@ -331,10 +316,7 @@ def write_layer_hashes(codec, bin_folder, hash_level=None):
     record = {"format_version": LAYER_HASH_FORMAT_VERSION, "level": hash_level, "layers": layers}
     path = _layer_path(bin_folder)
     _check_layer_record(path, record, gops)
-    with open(path, "w") as f:
-        json.dump(record, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=1)
 
 
 # ------------------------------------------------------------------------------------------------------------- extraction
@@ -342,19 +324,11 @@ def read_layer_extract(bin_folder):
     """-> None for a folder without layer_extract.json, else its record {"format_version", "min_level", "motion"};
     ValueError naming the path for a malformed file, another version or other fields"""
     path = os.path.join(bin_folder, LAYER_EXTRACT)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
+    record = read_record(path, "layer extract file", LAYER_EXTRACT_VERSION, fields=("min_level", "motion"),
+                         expected="format_version, min_level and motion")
+    if record is None:
         return None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a layer extract file ({e})") from None
-    if not isinstance(record, dict) or record.get("format_version") != LAYER_EXTRACT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {LAYER_EXTRACT_VERSION}")
-    if set(record) != {"format_version", "min_level", "motion"}:
-        raise ValueError(f"{path}: fields {sorted(record)}, expected format_version, min_level and motion")
-    if not _is_int(record["min_level"]) or record["min_level"] < 0 or not isinstance(record["motion"], bool):
+    if not is_int(record["min_level"]) or record["min_level"] < 0 or not isinstance(record["motion"], bool):
         raise ValueError(f"{path}: min_level {record['min_level']!r}, motion {record['motion']!r}")
     return record
 
@@ -401,14 +375,52 @@ def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     for rel in copies:
         os.makedirs(os.path.dirname(os.path.join(dst_folder, rel)), exist_ok=True)
         shutil.copyfile(os.path.join(src_folder, rel), os.path.join(dst_folder, rel))
-    with open(os.path.join(dst_folder, LAYER_EXTRACT), "w") as f:
-        json.dump({"format_version": LAYER_EXTRACT_VERSION, "min_level": level, "motion": bool(motion_fill)}, f, indent=1,
-                  sort_keys=True)
-        f.write("\n")
+    write_record(os.path.join(dst_folder, LAYER_EXTRACT),
+                 {"format_version": LAYER_EXTRACT_VERSION, "min_level": level, "motion": bool(motion_fill)}, indent=1)
     return sorted(copies + [LAYER_EXTRACT])
 
 
 # ------------------------------------------------------------------------------------------------------------ a sequence
+class LayerDecode(pmctf_gop.FullDecode):
+    """pmctf_gop.decode_sequence_with at a temporal level: every GOP through decode_gop_files_layer, the pictures checked
+    against picture_hashes.json where they are the full-rate ones (level 0, or a sequence of lone pictures: exactly
+    FullDecode's record) and against layer_hashes.json above; never under motion_fill.  The result gains "level", "times"
+    and "bytes_read"."""
+
+    def __init__(self, level, motion_fill=False):
+        _check_decode_args(level, motion_fill)
+        self.level, self.motion_fill = level, motion_fill
+
+    def refuse(self, verify):
+        if self.motion_fill and verify is True:
+            raise ValueError("motion_fill output is never verified: there is no record of it (verify=True refused)")
+
+    def check_folder(self, bin_folder):
+        _check_against_extract(bin_folder, self.level, self.motion_fill)
+
+    def open(self, bin_folder, header, gops, verify):
+        top = _max_level(gops)
+        self.full_rate = self.level == 0 or top == 0   # a sequence of lone pictures has one layer, the full-rate one
+        if self.motion_fill or verify is False:
+            return
+        if self.full_rate:
+            super().open(bin_folder, header, gops, verify)
+        elif verify != "auto" or os.path.exists(_layer_path(bin_folder)):
+            layers = read_layer_hashes(bin_folder)
+            self.frames, self.hash_level = layers["layers"][str(min(self.level, top))], layers["level"]
+
+    def decode_gop(self, codec, folder, size, h, w, q_index, psize, me_downsample, ll_order):
+        out = decode_gop_files_layer(codec, folder, size, h, w, q_index, self.level, psize=psize, me_downsample=me_downsample,
+                                     ll_order=ll_order, motion_fill=self.motion_fill)
+        return out["frames"], out["times"], out["bytes_read"]
+
+    def recorded(self, first, size, at, n):
+        return super().recorded(first, size, at, n) if self.full_rate else self.frames[at:at + n]
+
+    def result(self, times, nbytes):
+        return {"level": self.level, "times": times, "bytes_read": nbytes}
+
+
 def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False):
     """pmctf_gop.decode_sequence_checked at temporal level `level`: the folder's header (either kind), its
     picture_format.json (16-bit output above 8 bits, png_out refused) and the codec checks are the same, and every GOP is
@@ -427,95 +439,4 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
     (pmctf_chroma.decode_sequence_layer(..., coded_format_output=True): the coded 4:2:0 pictures).
     Returns decode_sequence's dict ("frames", "seconds", "verified", "hash_mismatches", "header", "bitdepth") plus "level",
     "times": the source index of every written picture, and "bytes_read": the sizes of the files read, layer_bytes."""
-    return _decode_sequence_layer(codec, bin_folder, yuv_out, level, device, png_out, verify, motion_fill)
-
-
-def _decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False,
-                           coded_size_output=False, coded_format_output=False):
-    """decode_sequence_layer's body; coded_size_output: pmctf_scale.decode_sequence_layer; coded_format_output:
-    pmctf_chroma.decode_sequence_layer"""
-    import contextlib
-    import time
-    import torch
-    G = pmctf_gop
-    _check_decode_args(level, motion_fill)
-    if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
-        raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
-    if motion_fill and verify is True:
-        raise ValueError("motion_fill output is never verified: there is no record of it (verify=True refused)")
-    if yuv_out is None and png_out is None:
-        raise ValueError("nothing to write: give yuv_out, png_out or both")
-    header, gops = G.sequence_layout(bin_folder)
-    _check_against_extract(bin_folder, level, motion_fill)
-    bitdepth = G.read_picture_format(bin_folder)
-    if bitdepth > 8 and png_out is not None:
-        raise ValueError(f"{os.path.join(bin_folder, G.PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
-                         f"8-bit PNGs; decode to a .yuv")
-    G.check_sequence_header(header, G.codec_header_fields(codec))
-    dev = codec.engine().dev
-    if device is not None and torch.device(device).type != dev.type:
-        raise ValueError(f"the codec lives on {dev}, not on {device}")
-    # the record the pictures are checked against: picture_hashes.json at level 0, layer_hashes.json above
-    recorded, hash_level = None, None
-    top = _max_level(gops)
-    if motion_fill or verify is False:
-        pass
-    elif level == 0 or top == 0:                   # a sequence of lone pictures has one layer, the full-rate one
-        if verify != "auto" or os.path.exists(os.path.join(bin_folder, G.PICTURE_HASHES)):
-            full = G.read_picture_hashes(bin_folder, header["frame_num"])
-            recorded, hash_level = full["frames"], full["level"]
-    elif verify != "auto" or os.path.exists(_layer_path(bin_folder)):
-        layers = read_layer_hashes(bin_folder)
-        recorded, hash_level = layers["layers"][str(min(level, top))], layers["level"]
-    h, w = header["height"], header["width"]
-    import pmctf_scale
-    display = pmctf_scale.display_size(bin_folder, w, h, dev, bitdepth, coded_size_output)
-    out_shape = (h, w) if display is None else display.size[::-1]
-    import pmctf_chroma
-    fmt = pmctf_chroma.output_format(bin_folder, yuv_out, w, h, display, dev, bitdepth, coded_format_output)
-    q_indexes = G.gop_q_indexes(header, len(gops))
-    shapes, seconds, mismatches, times = [], [], [], []
-    verified = at = nbytes = 0
-    with (open(yuv_out, "wb") if yuv_out is not None else contextlib.nullcontext()) as f:
-        if f is not None and fmt is not None:
-            f.write(fmt.stream_header)
-        for k, (first, size, psize, me_downsample) in enumerate(gops):
-            t0 = time.time()
-            folder = os.path.join(bin_folder, G.gop_folder(k))
-            out = decode_gop_files_layer(codec, folder, size, h, w, q_indexes[k], level, psize=psize,
-                                         me_downsample=me_downsample, ll_order=header["ll_order"], motion_fill=motion_fill)
-            source = [first + t for t in out["times"]]
-            if recorded is not None:
-                got = G.picture_hashes(out["frames"], h, w, hash_level, bitdepth)
-                want = recorded[first:first + size] if level == 0 or top == 0 else recorded[at:at + len(source)]
-                bad = []
-                for t, a, b in zip(source, got, want):
-                    bad += G.compare_hash_records([a], [b], t, gop=k, folder=folder)
-                if bad and verify != "report":
-                    raise G.PictureHashMismatch(bad[0])
-                mismatches += bad
-                verified += len(source)
-            if f is not None:
-                if fmt is not None:
-                    pictures = fmt.pictures(out["frames"])
-                elif display is not None:
-                    pictures = display.pictures(out["frames"])
-                else:
-                    pictures = G.frames_to_u16(out["frames"], h, w, bitdepth) if bitdepth > 8 else \
-                        G.frames_to_u8(out["frames"], h, w)
-                for planes in pictures:
-                    if fmt is not None:
-                        f.write(fmt.frame_marker)
-                    for p in planes:
-                        f.write(p.tobytes(order="C"))
-            if png_out is not None:
-                rgbs = G.frames_to_rgb8(out["frames"], h, w) if display is None else display.rgb8(out["frames"])
-                for t, rgb in zip(source, rgbs):
-                    G.write_pngs(png_out, t, [rgb])
-            at += len(source)
-            nbytes += out["bytes_read"]
-            times += source
-            shapes += [out_shape] * len(source)
-            seconds.append(time.time() - t0)
-    return {"header": header, "frames": shapes, "seconds": seconds, "verified": verified, "hash_mismatches": mismatches,
-            "bitdepth": bitdepth, "level": level, "times": times, "bytes_read": nbytes}
+    return pmctf_gop.decode_sequence_with(LayerDecode(level, motion_fill), codec, bin_folder, yuv_out, device, png_out, verify)

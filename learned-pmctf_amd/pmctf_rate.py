@@ -9,18 +9,15 @@ a few steps up or down the list of choices.  A leaky bucket carries what a GOP l
   verify_rate_record                          rate_control.json against the files and the header: no GPU, no codec
 The folder's gop_structure.json is format version 2 (a q_index in every GOP entry), which the decoders read.  Nothing
 here has a CPU path for the coding itself, and nothing here computes on pictures."""
-import json
 import os
+
+from pmctf_records import is_int, read_record, write_record
 
 RATE_RECORD = "rate_control.json"
 RATE_RECORD_VERSION = 1
 Q_NUM = 21                                            # pWave.get_qp_num(): q_index is one of 0..20
 RECORD_FIELDS = ("alloc", "budget", "q_index", "fits", "bits", "trials", "credit")
 PARAMETERS = ("bitrate", "fps", "q_choices", "q_start", "bucket_ms", "max_trials", "slack")
-
-
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
 
 
 def trial_folder(k, q):
@@ -30,16 +27,16 @@ def trial_folder(k, q):
 
 # ---------------------------------------------------------------------------------------------------------- the arguments
 def check_bitrate(bitrate):
-    if not _is_int(bitrate) or bitrate <= 0:
+    if not is_int(bitrate) or bitrate <= 0:
         raise ValueError(f"bitrate is a positive integer, in bits per second (got {bitrate!r})")
     return bitrate
 
 
 def check_fps(fps):
     """-> (num, den) of fps: a positive integer, or a pair (num, den) of positive integers"""
-    if _is_int(fps):
+    if is_int(fps):
         fps = (fps, 1)
-    if not isinstance(fps, (tuple, list)) or len(fps) != 2 or not all(_is_int(v) and v > 0 for v in fps):
+    if not isinstance(fps, (tuple, list)) or len(fps) != 2 or not all(is_int(v) and v > 0 for v in fps):
         raise ValueError(f"fps is a positive integer or a pair (num, den) of positive integers (got {fps!r})")
     return int(fps[0]), int(fps[1])
 
@@ -50,13 +47,13 @@ def check_q_choices(q_choices):
         q = tuple(q_choices)
     except TypeError:
         q = None
-    if not q or not all(_is_int(v) and 0 <= v < Q_NUM for v in q) or any(a >= b for a, b in zip(q, q[1:])):
+    if not q or not all(is_int(v) and 0 <= v < Q_NUM for v in q) or any(a >= b for a, b in zip(q, q[1:])):
         raise ValueError(f"q_choices is a strictly ascending sequence of integers of 0..{Q_NUM - 1} (got {q_choices!r})")
     return q
 
 
 def check_max_trials(max_trials):
-    if not _is_int(max_trials) or max_trials < 1:
+    if not is_int(max_trials) or max_trials < 1:
         raise ValueError(f"max_trials is an integer, at least 1 (got {max_trials!r})")
     return max_trials
 
@@ -68,7 +65,7 @@ def check_slack(slack):
 
 
 def check_bucket_ms(bucket_ms):
-    if not _is_int(bucket_ms) or bucket_ms < 0:
+    if not is_int(bucket_ms) or bucket_ms < 0:
         raise ValueError(f"bucket_ms is an integer, 0 or more, in milliseconds (got {bucket_ms!r})")
     return bucket_ms
 
@@ -77,7 +74,7 @@ def check_q_start(q_start, q_choices):
     """-> the index of q_start in q_choices; None: the middle one, q_choices[len // 2]"""
     if q_start is None:
         return len(q_choices) // 2
-    if not _is_int(q_start) or q_start not in q_choices:
+    if not is_int(q_start) or q_start not in q_choices:
         raise ValueError(f"q_start is one of q_choices {tuple(q_choices)} (got {q_start!r})")
     return q_choices.index(q_start)
 
@@ -94,7 +91,7 @@ def gop_allocations(gops, bitrate, fps):
     except (TypeError, KeyError, IndexError):
         raise ValueError(f"gops is a list of records that hold \"size\" (got {gops!r})") from None
     for k, size in enumerate(sizes):
-        if not _is_int(size) or size < 1:
+        if not is_int(size) or size < 1:
             raise ValueError(f"gops[{k}]: size is a positive integer (got {size!r})")
         out.append((size * bitrate * den) // num)
     return out
@@ -112,9 +109,9 @@ def choose_q(size_of, q_choices, start, budget, max_trials=4, slack=0.0):
     The accepted trial is the last one run or the one before it.
     -> {"q_index", "index", "fits", "bits", "trials": [(q, bits), ...] in the order run}"""
     q_choices = check_q_choices(q_choices)
-    if not _is_int(start) or not 0 <= start < len(q_choices):
+    if not is_int(start) or not 0 <= start < len(q_choices):
         raise ValueError(f"start is an index into the {len(q_choices)} q_choices (got {start!r})")
-    if not _is_int(budget):
+    if not is_int(budget):
         raise ValueError(f"budget is an integer, in bits (got {budget!r})")
     check_max_trials(max_trials)
     check_slack(slack)
@@ -122,7 +119,7 @@ def choose_q(size_of, q_choices, start, budget, max_trials=4, slack=0.0):
 
     def run(index):
         bits = size_of(q_choices[index])
-        if not _is_int(bits) or bits < 0:
+        if not is_int(bits) or bits < 0:
             raise ValueError(f"size_of({q_choices[index]}) is a count of bits (got {bits!r})")
         trials.append((q_choices[index], bits))
         return bits
@@ -192,7 +189,7 @@ def run_controller(gop_sizes, size_of, bitrate, fps, q_choices=range(Q_NUM), q_s
     ctl = Controller(bitrate, fps, q_choices, q_start, bucket_ms, max_trials, slack)
     sizes = list(gop_sizes)
     for k, size in enumerate(sizes):
-        if not _is_int(size) or size < 1:
+        if not is_int(size) or size < 1:
             raise ValueError(f"gop_sizes[{k}] is a positive integer (got {size!r})")
     return [ctl.gop(size, lambda q, k=k: size_of(k, q)) for k, size in enumerate(sizes)]
 
@@ -217,22 +214,22 @@ def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitra
     "bucket_bits", "gops": run_controller's records}; verify_rate_record checks it.
     Returns encode_sequence_gops' dictionary ("gops" with each GOP's "q_index"; the "average ms" lines count accepted
     trials only) plus "rate": run_controller's records, each with "seconds", the wall time of all the GOP's trials."""
-    return _encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device, structure,
-                                 hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
-                                 picture_hash, bitdepth, msssim, q_choices, q_start, bucket_ms, max_trials, slack)
+    return _encode_at_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device,
+                           structure=structure, hd_min=hd_min, mad_min=mad_min, ds_factors=ds_factors,
+                           skip_decoding=skip_decoding, psize=psize, src_format=src_format, ingest=ingest,
+                           decoded_frame_path=decoded_frame_path, picture_hash=picture_hash, bitdepth=bitdepth, msssim=msssim,
+                           q_choices=q_choices, q_start=q_start, bucket_ms=bucket_ms, max_trials=max_trials, slack=slack)
 
 
-def _encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device,
-                          structure="fill", hd_min=None, mad_min=None, ds_factors=(1, 2, 4, 8), skip_decoding=True, psize=128,
-                          src_format="yuv", ingest="host", decoded_frame_path=None, picture_hash=None, bitdepth=8,
-                          msssim=False, q_choices=range(Q_NUM), q_start=None, bucket_ms=1000, max_trials=4, slack=0.0,
-                          scale=None):
-    """encode_sequence_rate with `scale`, a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence_rate)"""
+def _encode_at_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device, *, pipeline=None,
+                    **options):
+    """encode_sequence_rate's body.  options: the controller's keywords (PARAMETERS) and those of pmctf_seq's GOP-list
+    body; pipeline: a pmctf_chroma.SourcePipeline or None."""
     import shutil
     import pmctf_gop
     import pmctf_seq
-    ctl = Controller(bitrate, fps, q_choices, q_start, bucket_ms, max_trials, slack)
-    if isinstance(structure, str) and structure == "search":
+    ctl = Controller(bitrate, fps, **{k: options.pop(k) for k in PARAMETERS[2:] if k in options})
+    if options.get("structure") == "search":
         raise ValueError("structure 'search' is refused with a bitrate: it ranks GOP sizes at one fixed q_index")
     records = []
     made = set()                                      # the trial folders of this call that still exist
@@ -282,11 +279,11 @@ def _encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitr
         records.append(dict(rec, seconds=spent))
         return accepted
 
-    out = pmctf_seq._encode_gop_list(codec, source, width, height, frame_num, max_gop, None, choose, bin_folder, device,
-                                     structure, pmctf_seq.HD_MIN if hd_min is None else hd_min,
-                                     pmctf_seq.MAD_MIN if mad_min is None else mad_min, ds_factors, skip_decoding, psize,
-                                     src_format, ingest, decoded_frame_path, picture_hash, bitdepth, msssim,
-                                     what="encode_sequence_rate", scale=scale)
+    for k, default in (("hd_min", pmctf_seq.HD_MIN), ("mad_min", pmctf_seq.MAD_MIN)):
+        if options.get(k) is None:
+            options[k] = default
+    out = pmctf_seq._encode_gop_list(codec, source, width, height, frame_num, max_gop, None, bin_folder, device,
+                                     choose=choose, pipeline=pipeline, what="encode_sequence_rate", **options)
     write_rate_record(bin_folder, ctl, [{f: r[f] for f in RECORD_FIELDS} for r in records])
     out["rate"] = records
     return out
@@ -298,29 +295,15 @@ def write_rate_record(bin_folder, ctl, records):
     path = os.path.join(bin_folder, RATE_RECORD)
     record = dict(ctl.parameters(), format_version=RATE_RECORD_VERSION, bucket_bits=ctl.bucket_bits,
                   gops=[dict(r, trials=[list(t) for t in r["trials"]]) for r in records])
-    with open(path, "w") as f:
-        json.dump(record, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=1)
 
 
 def read_rate_record(bin_folder):
     """-> the record of bin_folder/rate_control.json with its fields checked for form (verify_rate_record checks what
     they say); ValueError naming the path for a missing or malformed file, another version, unknown or missing fields"""
     path = os.path.join(bin_folder, RATE_RECORD)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        raise ValueError(f"{path}: missing (not a folder written with encode_sequence_rate)") from None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a rate control record ({e})") from None
-    if not isinstance(record, dict) or record.get("format_version") != RATE_RECORD_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this checker reads version {RATE_RECORD_VERSION}")
-    want = set(PARAMETERS) | {"format_version", "bucket_bits", "gops"}
-    if set(record) != want:
-        raise ValueError(f"{path}: fields missing {sorted(want - set(record))}, unknown {sorted(set(record) - want)}")
+    record = read_record(path, "rate control record", RATE_RECORD_VERSION, fields=PARAMETERS + ("bucket_bits", "gops"),
+                         missing="not a folder written with encode_sequence_rate", reader="checker")
     try:
         ctl = Controller(*(record[k] for k in PARAMETERS))
     except ValueError as e:
@@ -332,10 +315,10 @@ def read_rate_record(bin_folder):
     for k, r in enumerate(record["gops"]):
         if not isinstance(r, dict) or set(r) != set(RECORD_FIELDS):
             raise ValueError(f"{path}: gops[{k}] holds exactly {RECORD_FIELDS}")
-        if not all(_is_int(r[f]) for f in ("alloc", "budget", "q_index", "bits", "credit")) or not isinstance(r["fits"], bool):
+        if not all(is_int(r[f]) for f in ("alloc", "budget", "q_index", "bits", "credit")) or not isinstance(r["fits"], bool):
             raise ValueError(f"{path}: gops[{k}]: alloc, budget, q_index, bits and credit are integers, fits is true or false")
         if not isinstance(r["trials"], list) or not r["trials"] or not all(
-                isinstance(t, list) and len(t) == 2 and all(_is_int(v) for v in t) for t in r["trials"]):
+                isinstance(t, list) and len(t) == 2 and all(is_int(v) for v in t) for t in r["trials"]):
             raise ValueError(f"{path}: gops[{k}]: trials is a non-empty list of [q_index, bits]")
     return record
 

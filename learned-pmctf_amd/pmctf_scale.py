@@ -21,9 +21,10 @@ They are pmctf_gop's, pmctf_seq's, pmctf_rate's and pmctf_layers' functions with
 (encoding; what follows `device` is given by keyword) and coded_size_output (decoding) added; with coded_size=None they
 are those functions."""
 import functools
-import json
 import os
 from fractions import Fraction
+
+from pmctf_records import is_int, read_record, write_record
 
 COEF_BITS = 14
 COEF_ONE = 1 << COEF_BITS
@@ -34,10 +35,6 @@ CHROMA_LOCS = ("center", "left")
 DISPLAY_FORMAT = "display_format.json"
 DISPLAY_FORMAT_VERSION = 1
 DISPLAY_FIELDS = ("format_version", "width", "height", "filter", "chroma_loc")
-
-
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
 
 
 def catmull_rom(x):
@@ -54,7 +51,7 @@ def catmull_rom(x):
 def axis_table(n_in, n_out, phase=Fraction(0)):
     """-> (start: tuple of n_out ints, coef: tuple of n_out tuples of T ints, T) of one axis, as the module text defines
     them; rows shorter than T are zero-filled.  Cached per (n_in, n_out, phase)."""
-    if not _is_int(n_in) or not _is_int(n_out) or n_in < 1 or n_out < 1:
+    if not is_int(n_in) or not is_int(n_out) or n_in < 1 or n_out < 1:
         raise ValueError(f"an axis has positive integer lengths (got {n_in!r} -> {n_out!r})")
     phase = Fraction(phase)
     half = Fraction(1, 2)
@@ -87,7 +84,7 @@ def chroma_phase(n_in, n_out, chroma_loc):
 def check_sizes(src_w, src_h, dst_w, dst_h, what="size"):
     """both sizes even, positive, at most MAX_SIDE a side, and dst / src within [1/4, 4] on each axis; ValueError"""
     for n in (src_w, src_h, dst_w, dst_h):
-        if not _is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
+        if not is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
             raise ValueError(f"{what}: 4:2:0 pictures have even, positive sides up to {MAX_SIDE} "
                              f"(got {src_w!r}x{src_h!r} and {dst_w!r}x{dst_h!r})")
     for a, b in ((src_w, dst_w), (src_h, dst_h)):
@@ -115,25 +112,17 @@ def write_display_format(bin_folder, width, height, chroma_loc="center"):
     record = {"format_version": DISPLAY_FORMAT_VERSION, "width": width, "height": height, "filter": FILTER,
               "chroma_loc": chroma_loc}
     _check_display_record(path, record)
-    with open(path, "w") as f:
-        json.dump(record, f, indent=2, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=2)
 
 
 def _check_display_record(path, record, coded=None):
-    if not isinstance(record, dict) or record.get("format_version") != DISPLAY_FORMAT_VERSION:
-        got = record.get("format_version") if isinstance(record, dict) else None
-        raise ValueError(f"{path}: format version {got!r}, this decoder reads version {DISPLAY_FORMAT_VERSION}")
-    if set(record) != set(DISPLAY_FIELDS):
-        raise ValueError(f"{path}: fields {sorted(record)}, expected {sorted(DISPLAY_FIELDS)}")
     if record["filter"] != FILTER:
         raise ValueError(f"{path}: filter {record['filter']!r}, this decoder knows {FILTER!r}")
     if record["chroma_loc"] not in CHROMA_LOCS:
         raise ValueError(f"{path}: chroma_loc {record['chroma_loc']!r}, one of {CHROMA_LOCS}")
     w, h = record["width"], record["height"]
     for n in (w, h):
-        if not _is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
+        if not is_int(n) or n <= 0 or n & 1 or n > MAX_SIDE:
             raise ValueError(f"{path}: width and height are even, positive integers up to {MAX_SIDE} (got {w!r}x{h!r})")
     if coded is not None:
         try:
@@ -147,14 +136,10 @@ def read_display_format(bin_folder, coded_width=None, coded_height=None):
     naming the path for a malformed file, another version or filter, an unknown or missing field, a size that is not even
     and positive, and, when the coded size is given, a display size more than a factor of 4 from it"""
     path = os.path.join(bin_folder, DISPLAY_FORMAT)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        return None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a display format file ({e})") from None
-    _check_display_record(path, record, None if coded_width is None else (coded_width, coded_height))
+    record = read_record(path, "display format file", DISPLAY_FORMAT_VERSION, fields=DISPLAY_FIELDS,
+                         expected=sorted(DISPLAY_FIELDS))
+    if record is not None:
+        _check_display_record(path, record, None if coded_width is None else (coded_width, coded_height))
     return record
 
 
@@ -182,7 +167,7 @@ class Resampler:
 
     def __init__(self, src_w, src_h, dst_w, dst_h, device, bitdepth=8, chroma_loc="center"):
         check_sizes(src_w, src_h, dst_w, dst_h)
-        if not _is_int(bitdepth) or not 8 <= bitdepth <= 16:
+        if not is_int(bitdepth) or not 8 <= bitdepth <= 16:
             raise ValueError(f"bitdepth is 8 or 9..16 (got {bitdepth!r})")
         self.src, self.dst = (src_w, src_h), (dst_w, dst_h)
         self.bitdepth, self.chroma_loc, self.device = bitdepth, chroma_loc, device
@@ -218,20 +203,27 @@ def unpack_frame(frame, h, w, bitdepth=8):
 
 
 class _Ingest:
-    def __init__(self, coded, keep):
-        self.coded, self.keep = coded, keep
-        self.shape = coded.coded[::-1]                                # (height, width), as read_gop_device returns it
+    """The `resample` hook of a reader (pmctf_gop.read_gop_device applies it to every packed picture after upload): to
+    4:2:0 first (to420: a pmctf_chroma.Converter or None), then to the coded size (size: a CodedSize or None), which with
+    keep also keeps the 4:2:0 source picture for its display_quality.  shape: (height, width) of what comes out."""
+
+    def __init__(self, to420, size, keep, shape):
+        self.to420, self.size, self.keep, self.shape = to420, size, keep, shape
 
     def __call__(self, frame):
+        if self.to420 is not None:
+            frame = self.to420(frame)
+        if self.size is None:
+            return frame
         if self.keep:
-            self.coded.sources.append(frame)
-        return self.coded.down(frame)
+            self.size.sources.append(frame)
+        return self.size.down(frame)
 
 
 class CodedSize:
-    """What the encoders need to code a source of width x height at coded_size = (W, H): ingest(), the hook
-    read_gop_device applies to every packed picture after upload, the header, and the display quality of a reconstructed
-    GOP."""
+    """The "to coded size" step of a source's way into the codec (pmctf_chroma.SourcePipeline), for a 4:2:0 source of
+    width x height coded at coded_size = (W, H): the two Resamplers, the source pictures kept for the display quality of a
+    reconstructed GOP, and the header."""
 
     def __init__(self, width, height, coded_size, device, bitdepth=8, chroma_loc="center"):
         try:
@@ -249,7 +241,7 @@ class CodedSize:
     def ingest(self, keep):
         """the `resample` attribute of a reader (pmctf_gop.read_gop_device): frame -> coded-size frame; keep=True also
         keeps the source picture for display_quality"""
-        return _Ingest(self, keep)
+        return _Ingest(None, self, keep, self.coded[::-1])
 
     def write_header(self, bin_folder):
         return write_display_format(bin_folder, self.source[0], self.source[1], self.chroma_loc)
@@ -278,10 +270,13 @@ class CodedSize:
 
 
 class DisplaySize:
-    """What the decoders need to write the pictures of a folder with a display_format.json at their display size."""
+    """What the decoders need to write the pictures of a folder with a display_format.json at their display size: the
+    picture sink (pmctf_gop.picture_sink) of raw 4:2:0 output at that size."""
+    stream_header = frame_marker = b""
 
     def __init__(self, record, coded_width, coded_height, device, bitdepth=8):
         self.size = (record["width"], record["height"])
+        self.shape = self.size[::-1]
         self.coded = (coded_width, coded_height)
         self.bitdepth = bitdepth
         self.up = Resampler(coded_width, coded_height, record["width"], record["height"], device, bitdepth,
@@ -316,13 +311,17 @@ def display_size(bin_folder, coded_width, coded_height, device, bitdepth=8, code
     return DisplaySize(record, coded_width, coded_height, device, bitdepth)
 
 
-def _coded(width, height, coded_size, device, bitdepth, chroma_loc, what):
+def _pipeline(width, height, coded_size, device, bitdepth, chroma_loc, what):
+    """-> the pmctf_chroma.SourcePipeline of a 4:2:0 source coded at coded_size; None (no pipeline: the source enters the
+    codec as it is) without one"""
     import pmctf_gop
     if coded_size is None:
         chroma_phase(2, 2, chroma_loc)
         return None
+    import pmctf_chroma
     pmctf_gop._need_gpu(device, f"{what}(coded_size={coded_size!r})")
-    return CodedSize(width, height, coded_size, device, pmctf_gop.check_bitdepth(bitdepth), chroma_loc)
+    size = CodedSize(width, height, coded_size, device, pmctf_gop.check_bitdepth(bitdepth), chroma_loc)
+    return pmctf_chroma.SourcePipeline((width, height), chroma_loc=chroma_loc, size=size)
 
 
 # ---------------------------------------------------------------------------------------------------------- entry points
@@ -336,9 +335,9 @@ def encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin
     to width x height against the source.  chroma_loc: "center" (what the RGB conversion here produces) or "left".
     coded_size=None: pmctf_gop.encode_sequence itself."""
     import pmctf_gop
-    scale = _coded(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence")
-    return pmctf_gop._encode_sequence(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
-                                      scale=scale, **kwargs)
+    pipeline = _pipeline(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence")
+    return pmctf_gop._encode_equal_gops(codec, yuv_path, width, height, frame_num, gop, q_index, bin_folder, device,
+                                        pipeline=pipeline, **kwargs)
 
 
 def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device, *,
@@ -346,9 +345,9 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     """pmctf_seq.encode_sequence_gops with coded_size / chroma_loc as encode_sequence above has them; gop_structure.json
     carries the coded size and the folder gets display_format.json.  The scene-cut pass looks at the resampled pictures."""
     import pmctf_seq
-    scale = _coded(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence_gops")
-    return pmctf_seq._encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
-                                           scale=scale, **kwargs)
+    pipeline = _pipeline(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence_gops")
+    return pmctf_seq._encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
+                                      pipeline=pipeline, **kwargs)
 
 
 def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device, *,
@@ -356,9 +355,9 @@ def encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitra
     """pmctf_rate.encode_sequence_rate with coded_size / chroma_loc as encode_sequence above has them: the way to a
     bitrate below what the coarsest q_index reaches at the source's size."""
     import pmctf_rate
-    scale = _coded(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence_rate")
-    return pmctf_rate._encode_sequence_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder,
-                                            device, scale=scale, **kwargs)
+    pipeline = _pipeline(width, height, coded_size, device, kwargs.get("bitdepth", 8), chroma_loc, "encode_sequence_rate")
+    return pmctf_rate._encode_at_rate(codec, source, width, height, frame_num, max_gop, bitrate, fps, bin_folder, device,
+                                      pipeline=pipeline, **kwargs)
 
 
 def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", coded_size_output=False):
@@ -366,12 +365,14 @@ def decode_sequence_checked(codec, bin_folder, yuv_out, device=None, png_out=Non
     coded_size_output=True writes the pictures as they were coded (the ones the picture hashes describe) instead of
     resampling them to the display size."""
     import pmctf_gop
-    return pmctf_gop._decode_sequence(codec, bin_folder, yuv_out, device, png_out, verify, coded_size_output)
+    return pmctf_gop.decode_sequence_with(pmctf_gop.FullDecode(), codec, bin_folder, yuv_out, device, png_out, verify,
+                                          coded_size_output=coded_size_output)
 
 
 def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False,
                           coded_size_output=False):
     """pmctf_layers.decode_sequence_layer with coded_size_output as decode_sequence_checked above has it"""
+    import pmctf_gop
     import pmctf_layers
-    return pmctf_layers._decode_sequence_layer(codec, bin_folder, yuv_out, level, device, png_out, verify, motion_fill,
-                                               coded_size_output)
+    return pmctf_gop.decode_sequence_with(pmctf_layers.LayerDecode(level, motion_fill), codec, bin_folder, yuv_out, device,
+                                          png_out, verify, coded_size_output=coded_size_output)

@@ -13,11 +13,11 @@ or an explicit list of (size, me_downsample).
 A picture with no partner (a GOP of one) is coded by the L coder alone, as the L picture of a pair is.  The folder gets
 gop_structure.json (read_gop_structure) and no sequence.json: pmctf_gop.decode_sequence reads either.  Nothing here has a
 CPU path for the coding itself; plan_gops, scene_cuts and the header functions are pure Python."""
-import json
 import os
 
 import pmctf_gop
 from pmctf_gop import GOP_STRUCTURE, GOP_STRUCTURE_VERSION_Q      # 2: every GOP entry carries its own q_index (pmctf_rate)
+from pmctf_records import check_fields, is_int, read_record, write_record
 
 GOP_STRUCTURE_VERSION = 1                             # one q_index for the sequence
 STRUCTURE_FIELDS = ("width", "height", "frame_num", "max_gop", "q_index", "num_me_stages", "ll_order", "precision",
@@ -38,12 +38,8 @@ HD_MIN = 0.35
 MAD_MIN = 8.0
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def _power_of_two(v):
-    return _is_int(v) and v >= 1 and not v & (v - 1)
+    return is_int(v) and v >= 1 and not v & (v - 1)
 
 
 def plan_gops(frame_num, max_gop, cuts=()):
@@ -52,13 +48,13 @@ def plan_gops(frame_num, max_gop, cuts=()):
     GOP the largest power of two that is <= max_gop and <= what is left of its segment: sizes come from {1, 2, 4, ...,
     max_gop} and no GOP has a cut in its interior.  21 frames, max_gop 8, a cut at 5 -> sizes 4, 1, 8, 8.
     ValueError for bad arguments."""
-    if not _is_int(frame_num) or frame_num < 1:
+    if not is_int(frame_num) or frame_num < 1:
         raise ValueError(f"frame_num is a positive integer (got {frame_num!r})")
     if not _power_of_two(max_gop) or max_gop < 2:
         raise ValueError(f"max_gop is a power of two, at least 2 (got {max_gop!r})")
     cuts = list(cuts)
     for c in cuts:
-        if not _is_int(c) or not 1 <= c <= frame_num - 1:
+        if not is_int(c) or not 1 <= c <= frame_num - 1:
             raise ValueError(f"a cut is a picture index in 1..{frame_num - 1} (got {c!r})")
     out = []
     bounds = sorted(set(cuts)) + [frame_num]
@@ -96,7 +92,7 @@ def sequence_activity(reader_factory, frame_num, device, bitdepth=8):
     from pMCTF.hip import ops
     pmctf_gop._need_gpu(device, "sequence_activity")
     bitdepth = pmctf_gop.check_bitdepth(bitdepth)
-    if not _is_int(frame_num) or frame_num < 1:
+    if not is_int(frame_num) or frame_num < 1:
         raise ValueError(f"frame_num is a positive integer (got {frame_num!r})")
     reader = reader_factory()
     hists, sads, size = [], [], None
@@ -147,7 +143,7 @@ def _check_gops(where, gops, frame_num, max_gop, version=GOP_STRUCTURE_VERSION):
                               else "carries q_index, which belongs to version 2"))
         if not isinstance(g, dict) or set(g) != set(fields):
             raise ValueError(f"{where}: gops[{k}] holds exactly {fields}")
-        if not all(_is_int(g[f]) for f in fields):
+        if not all(is_int(g[f]) for f in fields):
             raise ValueError(f"{where}: gops[{k}]: every field is an integer ({g!r})")
         if version == GOP_STRUCTURE_VERSION_Q and not 0 <= g["q_index"] < Q_NUM:
             raise ValueError(f"{where}: gops[{k}]: q_index {g['q_index']} is not one of 0..{Q_NUM - 1}")
@@ -172,7 +168,7 @@ def _check_gops(where, gops, frame_num, max_gop, version=GOP_STRUCTURE_VERSION):
 def _check_structure(where, record):
     version = record["format_version"]
     for k in ("width", "height", "frame_num", "max_gop", "q_index", "num_me_stages", "aten_threads"):
-        if not _is_int(record[k]):
+        if not is_int(record[k]):
             raise ValueError(f"{where}: {k} is an integer (got {record[k]!r})")
     if record["width"] <= 0 or record["height"] <= 0 or (record["width"] | record["height"]) & 1 or record["frame_num"] < 1:
         raise ValueError(f"{where}: {record['frame_num']} pictures of {record['width']}x{record['height']}")
@@ -206,10 +202,7 @@ def write_gop_structure(bin_folder, **fields):
     record["gops"] = [dict(g) if isinstance(g, dict) else g for g in fields["gops"]] if isinstance(fields["gops"], list) \
         else fields["gops"]
     _check_structure(path, record)
-    with open(path, "w") as f:
-        json.dump(record, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return path
+    return write_record(path, record, indent=1)
 
 
 def read_gop_structure(bin_folder):
@@ -220,23 +213,15 @@ def read_gop_structure(bin_folder):
     a list that does not end at frame_num, a me_downsample outside {1, 2, 4, 8}, a psize other than
     ca_psize(me_downsample) or the sequence's own, and for a folder that also holds a sequence.json."""
     path = os.path.join(bin_folder, GOP_STRUCTURE)
-    try:
-        with open(path) as f:
-            record = json.load(f)
-    except FileNotFoundError:
-        raise ValueError(f"{path}: missing (not a folder written with encode_sequence_gops)") from None
-    except (json.JSONDecodeError, UnicodeDecodeError) as e:
-        raise ValueError(f"{path}: not a GOP structure file ({e})") from None
+    record = read_record(path, "GOP structure file", None, missing="not a folder written with encode_sequence_gops")
     if os.path.exists(os.path.join(bin_folder, pmctf_gop.SEQUENCE_HEADER)):
         raise ValueError(f"{path}: the folder also holds {pmctf_gop.SEQUENCE_HEADER}; a sequence has one header")
     versions = (GOP_STRUCTURE_VERSION, GOP_STRUCTURE_VERSION_Q)
-    if not isinstance(record, dict) or not _is_int(record.get("format_version")) or record["format_version"] not in versions:
+    if not isinstance(record, dict) or not is_int(record.get("format_version")) or record["format_version"] not in versions:
         got = record.get("format_version") if isinstance(record, dict) else None
         raise ValueError(f"{path}: format version {got!r}, this decoder reads version {GOP_STRUCTURE_VERSION} and version "
                          f"{GOP_STRUCTURE_VERSION_Q}")
-    want = set(STRUCTURE_FIELDS) | {"format_version"}
-    if set(record) != want:
-        raise ValueError(f"{path}: fields missing {sorted(want - set(record))}, unknown {sorted(set(record) - want)}")
+    check_fields(path, record, STRUCTURE_FIELDS)
     _check_structure(path, record)
     return record
 
@@ -249,11 +234,11 @@ def _explicit_structure(structure, frame_num, max_gop, psize):
         raise ValueError(f"structure is one of {STRUCTURES} or a list of (size, me_downsample) (got {structure!r})") from None
     gops, first = [], 0
     for size, ds in pairs:
-        if ds not in DS_FACTORS or not _is_int(ds):
+        if ds not in DS_FACTORS or not is_int(ds):
             raise ValueError(f"structure: me_downsample {ds!r} is not one of {DS_FACTORS}")
         gops.append({"first": first, "size": size, "me_downsample": ds,
                      "psize": psize if ds == 1 else pmctf_gop.ca_psize(ds)})
-        first += size if _is_int(size) else 0
+        first += size if is_int(size) else 0
     _check_gops("structure", gops, frame_num, max_gop)
     return gops
 
@@ -279,57 +264,36 @@ def encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_ind
     Returns encode_sequence's dictionary (frame_types: 0 for the first picture of every GOP, else 1; the two "average ms"
     lines only when a pair was coded) plus "gops": [{"first", "size", "me_downsample", "psize"}], and "cuts" and "activity"
     (scenecut), "searches": [{"first", "gop_choice", "ds_choice", "tested_opts", "trials"}] (search)."""
-    return _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, None, bin_folder, device, structure,
-                            hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
-                            picture_hash, bitdepth, msssim)
+    return _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device,
+                            structure=structure, hd_min=hd_min, mad_min=mad_min, ds_factors=ds_factors,
+                            skip_decoding=skip_decoding, psize=psize, src_format=src_format, ingest=ingest,
+                            decoded_frame_path=decoded_frame_path, picture_hash=picture_hash, bitdepth=bitdepth, msssim=msssim)
 
 
-def _encode_sequence_gops(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device, structure="fill",
-                          hd_min=HD_MIN, mad_min=MAD_MIN, ds_factors=DS_FACTORS, skip_decoding=True, psize=128,
-                          src_format="yuv", ingest="host", decoded_frame_path=None, picture_hash=None, bitdepth=8,
-                          msssim=False, scale=None):
-    """encode_sequence_gops with `scale`, a pmctf_scale.CodedSize or None (pmctf_scale.encode_sequence_gops)"""
-    return _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, None, bin_folder, device, structure,
-                            hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
-                            picture_hash, bitdepth, msssim, scale=scale)
-
-
-def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, choose, bin_folder, device, structure,
-                     hd_min, mad_min, ds_factors, skip_decoding, psize, src_format, ingest, decoded_frame_path,
-                     picture_hash, bitdepth, msssim, what="encode_sequence_gops", scale=None):
+def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, bin_folder, device, *, choose=None,
+                     pipeline=None, what="encode_sequence_gops", structure="fill", hd_min=HD_MIN, mad_min=MAD_MIN,
+                     ds_factors=DS_FACTORS, **options):
     """The body of encode_sequence_gops, shared with pmctf_rate.encode_sequence_rate.  choose is None: every GOP is coded
     once, at q_index, into its folder.  Otherwise q_index is None and choose(k, g, trial) decides GOP k's: trial(q, folder)
     codes the GOP (g: its entry of the list) at q into folder (created) and returns {"q_index", "folder", "bits": 8 x the
     sizes of its files, "seconds", ...}; choose returns the trial it accepts, whose files it has moved to
     bin_folder/gop_{k:05d}.  Only the accepted trial is reconstructed, reported and counted in the "average ms" lines; the
     GOP entries then carry "q_index" and the header is format version 2.
-    scale: a pmctf_scale.CodedSize, a pmctf_chroma.ChromaFormat (which also opens the reader of its source) or None.  With
-    one, every reader resamples its pictures on the device after upload
-    (read_gop_device, whatever `ingest` says; the scene-cut pass too), everything below sees a source of the coded size, the
-    header included, bin_folder gets display_format.json and the result "display_quality"."""
-    import io
+    options: encode_sequence's keywords (pmctf_gop.SequenceEncode, which raises their refusals).
+    pipeline: a pmctf_chroma.SourcePipeline or None.  With one, every reader converts its pictures on the device after
+    upload (read_gop_device, whatever `ingest` says; the scene-cut pass too), everything below sees a 4:2:0 source of the
+    coded size, the header included, bin_folder gets the pipeline's records and the result "display_quality"."""
     import time
     import torch
     G = pmctf_gop
-    if picture_hash is not None and picture_hash not in G.HASH_LEVELS:
-        raise ValueError(f"picture_hash is None or one of {G.HASH_LEVELS} (got {picture_hash!r})")
-    bitdepth = G.check_bitdepth(bitdepth)
-    if picture_hash is not None:
-        G.check_hash_level(picture_hash, bitdepth)
-    if bitdepth > 8:
-        if src_format == "png":
-            raise ValueError(f"bitdepth {bitdepth}: a source above 8 bits is a .yuv file (src_format='yuv'), PNG input is 8-bit")
-        if msssim:
-            raise ValueError(f"bitdepth {bitdepth}: MS-SSIM and RGB-PSNR are defined on 8-bit RGB pictures (msssim=False)")
-        if decoded_frame_path is not None:
-            raise ValueError(f"bitdepth {bitdepth}: decoded_frame_path writes 8-bit PNGs; decode the folder to a .yuv instead")
-    if src_format not in ("yuv", "png") or ingest not in ("host", "device"):
-        raise ValueError(f"src_format is 'yuv' or 'png' and ingest 'host' or 'device' (got {src_format!r}, {ingest!r})")
-    if not _is_int(frame_num) or frame_num < 1:
+    e = G.SequenceEncode(pipeline, keep_gops=True, **options)
+    e.check_source_kind()
+    skip_decoding, psize = e.skip_decoding, e.psize
+    if not is_int(frame_num) or frame_num < 1:
         raise ValueError(f"frame_num is a positive integer (got {frame_num!r})")
     if not _power_of_two(max_gop) or max_gop < 2:
         raise ValueError(f"max_gop is a power of two, at least 2 (got {max_gop!r})")
-    if not _is_int(psize) or psize <= 0 or psize & 1:
+    if not is_int(psize) or psize <= 0 or psize & 1:
         raise ValueError(f"psize must be even and positive (got {psize!r})")
     plan = None                                                       # [{"first","size","me_downsample","psize"}] known ahead
     if isinstance(structure, str):
@@ -343,26 +307,9 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
                 raise ValueError(f"ds_factors: a non-empty choice of {DS_FACTORS} (got {ds_factors!r})")
     else:
         plan = _explicit_structure(structure, frame_num, max_gop, psize)
-    from pMCTF.utils.video_eval_utils import dump_json, generate_log_json
-    from pMCTF.utils.yuv_reader import YUVReader
-    on_device = src_format == "png" or ingest == "device" or scale is not None
-    if on_device or structure == "scenecut":
-        G._need_gpu(device, f"{what}(src_format={src_format!r}, ingest={ingest!r}, structure={structure!r})")
-
-    def make_reader(keep=False):
-        if src_format == "png":
-            reader = G.PNGReader(source)
-            if (reader.width, reader.height) != (width, height):
-                raise ValueError(f"the pictures are {reader.width}x{reader.height}, not {width}x{height}")
-            if len(reader) < frame_num:
-                raise ValueError(f"{frame_num} frames asked for, {len(reader)} pictures found")
-        else:
-            reader = (getattr(scale, "open_reader", None) or YUVReader)(source, width, height, start_index=0,
-                                                                        bitdepth=bitdepth)
-        if scale is not None:
-            reader.resample = scale.ingest(keep)
-        return reader
-
+    if e.on_device or structure == "scenecut":
+        G._need_gpu(device, f"{what}(src_format={e.src_format!r}, ingest={e.ingest!r}, structure={structure!r})")
+    make_reader = lambda keep=False: e.open_reader(source, width, height, frame_num, keep)
     t0 = time.time()
     extra = {}
     unit = lambda first, size, ds=1, ps=psize: {"first": first, "size": size, "me_downsample": ds, "psize": ps}
@@ -370,20 +317,16 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
         plan = [unit(f, s) for f, s in plan_gops(frame_num, max_gop)]
     elif structure == "scenecut":
         with torch.no_grad():
-            extra["activity"] = sequence_activity(make_reader, frame_num, device, bitdepth)
+            extra["activity"] = sequence_activity(make_reader, frame_num, device, e.bitdepth)
         extra["cuts"] = scene_cuts(extra["activity"]["mad"], extra["activity"]["hd"], hd_min, mad_min)
         plan = [unit(f, s) for f, s in plan_gops(frame_num, max_gop, extra["cuts"])]
     elif structure == "search":
         extra["searches"] = []
     reader = make_reader(keep=True)
-    display = []
-    if scale is not None:
-        width, height = scale.coded
-    read = G.read_gop_device if on_device else G.read_gop
-    tables = {k: [] for k in ("bits", "bpp_mv", "psnr", "psnr_rgb", "frame_types")}
-    lines, ssims, hashes, gops = [], [], [], []
-    pairs = 0
-    seconds = {"encoding_time": 0.0, "decoding_time": 0.0}
+    if pipeline is not None:
+        width, height = pipeline.coded
+    read = lambda size, ps: e.read_gop(reader, size, device, ps)
+    gops = []
 
     def trial(g, padded, h, w, q, folder):
         """one GOP coded once, at q, into folder: its files and what report needs of it"""
@@ -403,46 +346,34 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
             t["bits"] = 8 * sum(os.path.getsize(os.path.join(folder, n)) for n in names)
         return t
 
-    def report(g, t, orig, h, w):
-        """the accepted coding of a GOP: its reconstruction, its rows of the tables"""
-        nonlocal pairs
-        if g["size"] == 1:
-            r = t["lone"]
-            rec, bits, bits_mv = [[r["L_t"], r["L_tc"], None]], [float(r["bit_L"])], [0.0]
-        else:
-            enc = t["enc"]
-            for r in enc["results"]:
-                pairs += 1
-                for key in seconds:
-                    seconds[key] += r[key]
-            lines.extend(enc["log"])
-            rec, bits, bits_mv = G.decode_gop(codec, enc["frames_coded"]), enc["bits"], enc["bits_mv"]
-        G.report_gop(rec, orig, h, w, bits, bits_mv, g["first"], tables, ssims, hashes, picture_hash=picture_hash,
-                     bitdepth=bitdepth, decoded_frame_path=decoded_frame_path, msssim=msssim)
-        if scale is not None:
-            display.extend(scale.display_quality(rec))
-        gops.append(dict(g) if choose is None else dict(g, q_index=t["q_index"]))
-
     def code(g, padded, orig, h, w):
-        """one GOP of the list: its folder, its files, its reconstruction, its rows of the tables"""
+        """one GOP of the list: its folder, its files, and of the accepted coding the reconstruction and the tables' rows"""
         k = len(gops)
         if choose is None:
             t = trial(g, padded, h, w, q_index, os.path.join(bin_folder, G.gop_folder(k)))
         else:
             t = choose(k, dict(g), lambda q, folder: trial(g, padded, h, w, q, folder))
-        report(g, t, orig, h, w)
+        if g["size"] == 1:
+            r = t["lone"]
+            rec, bits, bits_mv = [[r["L_t"], r["L_tc"], None]], [float(r["bit_L"])], [0.0]
+        else:
+            enc = t["enc"]
+            e.add_pairs(enc)
+            rec, bits, bits_mv = G.decode_gop(codec, enc["frames_coded"]), enc["bits"], enc["bits_mv"]
+        e.add_gop(rec, orig, h, w, bits, bits_mv, g["first"])
+        gops.append(dict(g) if choose is None else dict(g, q_index=t["q_index"]))
 
     try:
         with torch.no_grad():
             if plan is not None:
                 for g in plan:
-                    padded, orig, (h, w) = read(reader, g["size"], device, g["psize"])
+                    padded, orig, (h, w) = read(g["size"], g["psize"])
                     code(g, padded, orig, h, w)
             else:
                 import pmctf_ca
                 first = 0
                 while frame_num - first >= max_gop:
-                    _, orig, (h, w) = read(reader, max_gop, device, psize)
+                    _, orig, (h, w) = read(max_gop, psize)
                     s = pmctf_ca.search_gop(codec, orig, h, w, q_index, None, write_stream=False,
                                             skip_decoding=skip_decoding, ds_factors=ds_factors)
                     size, ds = s["gop_choice"], s["ds_choice"]
@@ -456,31 +387,14 @@ def _encode_gop_list(codec, source, width, height, frame_num, max_gop, q_index, 
                     first += max_gop
                 if first < frame_num:
                     for f, s in plan_gops(frame_num - first, max_gop):
-                        padded, orig, (h, w) = read(reader, s, device, psize)
+                        padded, orig, (h, w) = read(s, psize)
                         code(unit(first + f, s), padded, orig, h, w)
     finally:
         reader.close()
     write_gop_structure(bin_folder, width=width, height=height, frame_num=frame_num, max_gop=max_gop,
                         q_index=q_index if choose is None else gops[0]["q_index"],
                         ll_order="plane" if skip_decoding else "position", gops=gops, **G.codec_header_fields(codec))
-    if picture_hash is not None:
-        G.write_picture_hashes(bin_folder, picture_hash, hashes)
-    if bitdepth > 8:
-        G.write_picture_format(bin_folder, bitdepth)
-    if scale is not None:
-        scale.write_header(bin_folder)
-    if pairs:
-        for key, label in (("encoding_time", "encoding"), ("decoding_time", "decoding")):
-            lines.append(f"{label} {pairs} P frames, average {seconds[key] / pairs * 1000:.0f} ms.")
-    record = generate_log_json(frame_num, tables["frame_types"], tables["bits"], tables["bpp_mv"], tables["psnr"],
-                               tables["psnr_rgb"], ssims if msssim else [0] * frame_num, height * width, time.time() - t0)
-    text = io.StringIO()
-    dump_json(record, text, float_digits=6, indent=2)
-    out = dict(tables, log=record, json=text.getvalue(), lines=lines, gops=gops, **extra)
-    if msssim:
-        out["msssim"] = ssims
-    if picture_hash is not None:
-        out["picture_hashes"] = hashes
-    if scale is not None:
-        out["display_quality"] = display
-    return out
+    e.write_sidecars(bin_folder)
+    if e.pairs:
+        e.average_lines()
+    return e.result(frame_num, width, height, t0, gops=gops, **extra)

@@ -22,14 +22,16 @@ FPS = (1, 24, 30, 60, (30000, 1001), (24000, 1001), (25, 2), (7, 3))
 
 
 def test_the_module_imports_no_torch_at_module_level():
-    tree = ast.parse(open(os.path.join(ROOT, "learned-pmctf_amd", "pmctf_rate.py")).read())
-    top = set()
-    for node in tree.body:
-        if isinstance(node, ast.Import):
-            top |= {a.name.split(".")[0] for a in node.names}
-        elif isinstance(node, ast.ImportFrom):
-            top.add((node.module or "").split(".")[0])
-    assert top == {"json", "os"}, top
+    # pmctf_rate reads and writes its record through pmctf_records, which is held to the standard library alone
+    for name, allowed in (("pmctf_rate.py", {"os", "pmctf_records"}), ("pmctf_records.py", {"json"})):
+        tree = ast.parse(open(os.path.join(ROOT, "learned-pmctf_amd", name)).read())
+        top = set()
+        for node in tree.body:
+            if isinstance(node, ast.Import):
+                top |= {a.name.split(".")[0] for a in node.names}
+            elif isinstance(node, ast.ImportFrom):
+                top.add((node.module or "").split(".")[0])
+        assert top == allowed, (name, top)
 
 
 # ------------------------------------------------------------------------------------------------------- the size tables
