@@ -377,7 +377,8 @@ int pmctf_ll_ar_decode_batch_f32(const pmctf_ll_job *jobs_dev, int n_jobs, const
                                  const int32_t *offsets, int cdf_cols, float log_scale_min, float log_scale_step, int P,
                                  int H, int W, int plane_order, void *stream);
 /* Decoder output stage: padded float planes (N,1,Hp,Wp) -> cropped 8-bit planes (N,h,w), rint(clamp(x, 0, 255)) with ties
- * to even (torch.round), NaN -> 0.  h <= Hp, w <= Wp. */
+ * to even (torch.round), NaN -> 0.  h <= Hp, w <= Wp, N*Hp*Wp < 2^31; out at any address.  The uint8_t instantiation of
+ * the body of pmctf_planes_to_u16 (csrc/picture_ops.hip). */
 int pmctf_planes_to_u8(const float *x, uint8_t *out, int N, int Hp, int Wp, int h, int w, void *stream);
 /* ContextFusionFourStep.decompress (context_fusion_4step.py:196-249): CDF rows handed to decode_stream for step k
  * (0 off the mask), then x_hat = (q + mean) on the mask.  params as in pmctf_fourstep_quant_f32. */
@@ -467,7 +468,7 @@ int pmctf_yuv420_u8_to_planes_f32(const uint8_t *src, float *y_pad, float *c_pad
 int pmctf_rgb8_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int h, int w, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * High-bit-depth pictures in and out (csrc/picture_hbd.hip): planar 4:2:0 sources of bitdepth b = 9..16, every sample a
+ * High-bit-depth pictures in and out (the uint16_t instantiations of csrc/picture_ops.hip, and csrc/picture_hbd.hip): planar 4:2:0 sources of bitdepth b = 9..16, every sample a
  * little-endian 16-bit word (yuv420p10le / p12le / p16le).  The codec's float planes keep their 0..255 range: with
  * s = b - 8 and max = 2^b - 1 a sample v enters as v * 2^-s (exact for every 16-bit v) and a reconstruction x leaves as
  * rint(clamp(x * 2^s, 0, max)), ties to even, NaN -> 0; out(in(v)) == v for every v <= max.  No synchronisation.

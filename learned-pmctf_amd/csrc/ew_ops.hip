@@ -375,32 +375,6 @@ __global__ void ll_quant_kernel(const float *__restrict__ ll, const float *__res
     }
 }
 
-// Decoder output stage: padded float planes [N][Hp][Wp] -> cropped 8-bit planes [N][h][w], rint(clamp(x, 0, 255)) (ties to
-// even: torch.round).  The output is one flat byte array: a thread converts four consecutive bytes (they may straddle a
-// row end when w % 4 != 0) and writes them with one 4-byte store; the last total % 4 bytes are written one by one.
-__device__ __forceinline__ unsigned px_u8(const float *__restrict__ x, int i, int h, int w, int Hp, int Wp) {
-    const int row = i / w, col = i - row * w;
-    const int n = row / h, y = row - n * h;
-    float t = x[((long)n * Hp + y) * Wp + col];
-    t = t < 0.0f ? 0.0f : t;
-    t = t > 255.0f ? 255.0f : t;
-    return (unsigned)(int)__builtin_rintf(t);
-}
-
-__global__ void planes_to_u8_kernel(const float *__restrict__ x, uint8_t *out, int N, int Hp, int Wp, int h, int w) {
-    const int total = N * h * w, quads = total >> 2;
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += gridDim.x * blockDim.x) {
-        const int i = q << 2;
-        const unsigned v = px_u8(x, i, h, w, Hp, Wp) | (px_u8(x, i + 1, h, w, Hp, Wp) << 8) |
-                           (px_u8(x, i + 2, h, w, Hp, Wp) << 16) | (px_u8(x, i + 3, h, w, Hp, Wp) << 24);
-        *(unsigned *)(out + i) = v;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (total & 3)) {
-        const int i = (quads << 2) + threadIdx.x;
-        out[i] = (uint8_t)px_u8(x, i, h, w, Hp, Wp);
-    }
-}
-
 // MV hyper latent: z_hat = round(z) (NHWC), push in NCHW order with CDF row = channel (entropy_models.py:180-193)
 __global__ void z_symbols_kernel(const float *__restrict__ z, float *z_hat, short *sym, short *idx, int HW, int C) {
     const long total = (long)HW * C;
@@ -619,15 +593,6 @@ extern "C" int pmctf_ll_quant_f32(const float *ll, const float *params, float *l
         return PMCTF_EINVAL;
     PM_LAUNCH(ll_quant_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, ll, params, ll_hat, sym,
                        idx, (long)total, planes, log_scale_min, log_scale_step);
-    return launch_ok();
-}
-
-extern "C" int pmctf_planes_to_u8(const float *x, uint8_t *out, int N, int Hp, int Wp, int h, int w, void *stream) {
-    if (!x || !out || N <= 0 || h <= 0 || w <= 0 || h > Hp || w > Wp || ((uintptr_t)out & 3) ||
-        (long)N * Hp * Wp > 0x7fffffffL)
-        return PMCTF_EINVAL;
-    PM_LAUNCH(planes_to_u8_kernel, dim3(grid_for(((long)N * h * w + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, out, N,
-              Hp, Wp, h, w);
     return launch_ok();
 }
 

@@ -19,7 +19,7 @@
 #include "picture_resample.h"
 
 #define C_SLOTS 4                                        // 16-byte slots per thread
-#define C_CHUNK (S_THREADS * 16 * C_SLOTS)               // bytes of the destination per copy block
+#define C_CHUNK (P_THREADS * 16 * C_SLOTS)               // bytes of the destination per copy block
 #define C_TAPS 17                                        // longest table row accepted (2:1 needs 7, 1:2 needs 4)
 
 struct ChromaArgs {
@@ -65,7 +65,7 @@ __device__ __forceinline__ void copy_block(const uint8_t *__restrict__ src, uint
     const ptrdiff_t first = (ptrdiff_t)b * C_CHUNK - lead;               // offset of the chunk from dst (and from src)
 #pragma unroll
     for (int i = 0; i < C_SLOTS; ++i) {
-        const ptrdiff_t o = first + ((ptrdiff_t)i * S_THREADS + threadIdx.x) * 16;
+        const ptrdiff_t o = first + ((ptrdiff_t)i * P_THREADS + threadIdx.x) * 16;
         if (o >= 0 && (size_t)o + 16 <= n) {
             copy_slot<G>(src + o, dst + o);
         } else {
@@ -75,7 +75,7 @@ __device__ __forceinline__ void copy_block(const uint8_t *__restrict__ src, uint
 }
 
 template <typename S>
-__global__ __launch_bounds__(S_THREADS) void convert_chroma_kernel(const S *__restrict__ src, S *__restrict__ dst,
+__global__ __launch_bounds__(P_THREADS) void convert_chroma_kernel(const S *__restrict__ src, S *__restrict__ dst,
                                                                     const ChromaArgs a, int top) {
     __shared__ __attribute__((aligned(16))) int tmp[S_ROWS * S_TW];
     __shared__ int cx[S_TAPS * S_TW];
@@ -113,7 +113,6 @@ __global__ __launch_bounds__(S_THREADS) void convert_chroma_kernel(const S *__re
         resample_tile<S, false, false>(src, dst, P, tile, top, tmp, cx);
 }
 
-static bool side_ok(int n) { return n > 0 && !(n & 1) && n <= S_MAX_SIDE; }
 static bool taps_ok(int t) { return t >= 1 && t <= C_TAPS; }
 
 // the subsampling (sx, sy) of a format given as 420, 422 or 444; false for anything else
@@ -145,7 +144,7 @@ static int convert_chroma(const S *src, S *dst, int h, int w, int fmt_in, int fm
     }
     a.copy_blocks = (unsigned)((((uintptr_t)dst & 15) + a.copy_bytes + C_CHUNK - 1) / C_CHUNK);
     const unsigned blocks = a.copy_blocks + a.p[0].tiles + a.p[1].tiles;
-    PM_LAUNCH(convert_chroma_kernel<S>, dim3(blocks), dim3(S_THREADS), 0, (hipStream_t)stream, src, dst, a,
+    PM_LAUNCH(convert_chroma_kernel<S>, dim3(blocks), dim3(P_THREADS), 0, (hipStream_t)stream, src, dst, a,
               (1 << bitdepth) - 1);
     return pm_launch_status();
 }
@@ -160,6 +159,6 @@ extern "C" int pmctf_convert_chroma_u8(const uint8_t *src, uint8_t *dst, int h, 
 extern "C" int pmctf_convert_chroma_u16(const uint16_t *src, uint16_t *dst, int h, int w, int fmt_in, int fmt_out,
                                         const void *chroma_x, const void *chroma_y, const int taps[2], int bitdepth,
                                         void *stream) {
-    if (bitdepth < 9 || bitdepth > 16) return PMCTF_EINVAL;
+    if (!depth_ok(bitdepth)) return PMCTF_EINVAL;
     return convert_chroma<uint16_t>(src, dst, h, w, fmt_in, fmt_out, chroma_x, chroma_y, taps, bitdepth, stream);
 }

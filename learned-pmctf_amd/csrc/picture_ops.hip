@@ -1,28 +1,25 @@
-// Pictures in and out of the codec as gfx950 kernels; three streaming kernels, one launch each:
+// Pictures in and out of the codec as gfx950 kernels; four streaming kernels, one launch each:
 //   yuv420_to_rgb8_kernel      reconstruction (padded float planes) -> interleaved RGB bytes [h][w][3], the picture the
 //                              harness saves as a PNG (test_pMCTF_flex.py:76-79,301-317,334-336): the rounded RGB picture
 //                              of quality_front_kernel, clipped to 0..255
-//   yuv420_u8_to_planes_kernel one picture as it lies in a .yuv file -> the model's zero-padded float inputs and,
+//   yuv420_to_planes_kernel<S> one picture as it lies in a .yuv file -> the model's zero-padded float inputs and,
 //                              optionally, the un-padded originals (test_pMCTF_flex.py:151-192)
 //   rgb8_to_yuv420_u8_kernel   RGB bytes -> planar 8-bit 4:2:0 (rgb2ycbcr, pMCTF/utils/util.py:21-40, 2x2 chroma mean)
-// All three index their OUTPUT flat from its base address in groups of four elements, so that the wide stores are aligned
-// whatever the picture's width is; a wide access to the other side is taken when its address allows it, narrower ones
-// otherwise (the Cr plane of a .yuv picture starts at an odd byte for some sizes).
+//   planes_to_samples_kernel<S> padded float planes -> cropped planes of samples, the decoder's output stage
+// S is the sample type: uint8_t at bit depth 8, uint16_t (little-endian words of a 16-bit .yuv file) at b = 9..16.  With
+// s = b - 8 and max = 2^b - 1 a sample v comes in as x = v * 2^-s (exact for every 16-bit v; no multiplication at 8 bits)
+// and goes out as rint(clamp(x * 2^s, 0, max)), ties to even, NaN -> 0: both factors are powers of two, so
+// out(in(v)) == v for every v <= max.
+// All four index their OUTPUT flat from its base address in groups of four elements; a wide access to either side is
+// taken when its address allows it, narrower ones otherwise (picture_common.h: load4, store4).  The Cr plane of a .yuv
+// picture starts at an odd byte (halfword) for some sizes, and the cropped chroma of a 6x10 picture is 3x5.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/pmctf_hip.h"
 #include "launch.h"
+#include "picture_common.h"
 #include "picture_math.h"
-
-#define P_THREADS 256
-#define P_MAX_SIDE 16384                         // a plane has at most 2^28 samples: flat indices fit 32 bits
-
-static bool size_ok(int h, int w) { return h > 0 && w > 0 && !((h | w) & 1) && h <= P_MAX_SIDE && w <= P_MAX_SIDE; }
-static bool padded_ok(int Hp, int Wp, int h, int w) {
-    return Hp >= h && Wp >= w && !((Hp | Wp) & 1) && Hp <= P_MAX_SIDE && Wp <= P_MAX_SIDE;
-}
-static dim3 grid_of(long items) { return dim3((unsigned)((items + P_THREADS - 1) / P_THREADS)); }
 
 // ------------------------------------------------------------------------------------------------ (a) YUV 4:2:0 -> RGB
 // One thread makes four consecutive pixels of the flat output: 12 bytes, three aligned dwords (h * w is a multiple of 4).
@@ -76,10 +73,18 @@ extern "C" int pmctf_yuv420_to_rgb8_f32(const float *rec_y, const float *rec_c, 
 }
 
 // ------------------------------------------------------------------------------------- (b) .yuv picture -> float planes
-// `planes` planes of rows x cols bytes at src -> pad [planes][Rp][Cp] (zero outside the picture) and, if org is not null,
+// a sample as the model's float: v at 8 bits, v * down at more (down = 2^-(b - 8))
+template <typename S>
+__device__ __forceinline__ float to_float(unsigned v, float down) {
+    if constexpr (sizeof(S) == 1) return (float)v;
+    else return (float)v * down;
+}
+
+// `planes` planes of rows x cols samples at src -> pad [planes][Rp][Cp] (zero outside the picture) and, if org is not null,
 // org [planes][rows][cols].  Group g holds the flat elements 4g .. 4g + 3 of pad (fewer at the very end).
-__device__ __forceinline__ void planes_group(const uint8_t *__restrict__ src, float *__restrict__ pad, float *__restrict__ org,
-                                             unsigned g, int planes, int Rp, int Cp, int rows, int cols) {
+template <typename S>
+__device__ __forceinline__ void planes_group(const S *__restrict__ src, float *__restrict__ pad, float *__restrict__ org,
+                                             unsigned g, int planes, int Rp, int Cp, int rows, int cols, float down) {
     const unsigned plane_p = (unsigned)Rp * (unsigned)Cp, total = (unsigned)planes * plane_p;
     const unsigned plane_o = (unsigned)rows * (unsigned)cols;
     const unsigned i0 = 4u * g;
@@ -89,16 +94,17 @@ __device__ __forceinline__ void planes_group(const uint8_t *__restrict__ src, fl
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (r < rows && c < cols) {
             const size_t at = (size_t)p * plane_o + (size_t)r * (unsigned)cols + (unsigned)c;
-            const uint8_t *s = src + at;
+            const S *s = src + at;
             const bool whole = c + 3 < cols;
-            if (whole && !((uintptr_t)s & 3)) {
-                const uint32_t u = *reinterpret_cast<const uint32_t *>(s);
-                v[0] = (float)(u & 255u); v[1] = (float)((u >> 8) & 255u);
-                v[2] = (float)((u >> 16) & 255u); v[3] = (float)(u >> 24);
+            if (whole) {
+                unsigned u[4];
+                load4(s, u);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = to_float<S>(u[k], down);
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (c + k < cols) v[k] = (float)s[k];
+                    if (c + k < cols) v[k] = to_float<S>(s[k], down);
             }
             if (org) {
                 float *o = org + at;
@@ -120,34 +126,48 @@ __device__ __forceinline__ void planes_group(const uint8_t *__restrict__ src, fl
         float v = 0.0f;
         if (rr < rows && cc < cols) {
             const size_t at = (size_t)pp * plane_o + (size_t)rr * (unsigned)cols + (unsigned)cc;
-            v = (float)src[at];
+            v = to_float<S>(src[at], down);
             if (org) org[at] = v;
         }
         pad[i] = v;
     }
 }
 
-__global__ __launch_bounds__(P_THREADS) void yuv420_u8_to_planes_kernel(const uint8_t *__restrict__ src,
-                                                                         float *__restrict__ y_pad, float *__restrict__ c_pad,
-                                                                         float *__restrict__ y_org, float *__restrict__ c_org,
-                                                                         int Hp, int Wp, int h, int w, unsigned groups_y,
-                                                                         unsigned groups_c) {
+template <typename S>
+__global__ __launch_bounds__(P_THREADS) void yuv420_to_planes_kernel(const S *__restrict__ src, float *__restrict__ y_pad,
+                                                                      float *__restrict__ c_pad, float *__restrict__ y_org,
+                                                                      float *__restrict__ c_org, int Hp, int Wp, int h, int w,
+                                                                      float down, unsigned groups_y, unsigned groups_c) {
     const unsigned g = blockIdx.x * P_THREADS + threadIdx.x;
     if (g < groups_y)
-        planes_group(src, y_pad, y_org, g, 1, Hp, Wp, h, w);
+        planes_group(src, y_pad, y_org, g, 1, Hp, Wp, h, w, down);
     else if (g - groups_y < groups_c)
-        planes_group(src + (size_t)h * (unsigned)w, c_pad, c_org, g - groups_y, 2, Hp >> 1, Wp >> 1, h >> 1, w >> 1);
+        planes_group(src + (size_t)h * (unsigned)w, c_pad, c_org, g - groups_y, 2, Hp >> 1, Wp >> 1, h >> 1, w >> 1, down);
+}
+
+// bitdepth: 8 for uint8_t, checked by the entry for uint16_t
+template <typename S>
+static int yuv420_to_planes(const S *src, float *y_pad, float *c_pad, float *y_org, float *c_org, int Hp, int Wp, int h, int w,
+                            int bitdepth, void *stream) {
+    if (!src || !y_pad || !c_pad || !size_ok(h, w) || !padded_ok(Hp, Wp, h, w) || ((uintptr_t)src & (sizeof(S) - 1)) ||
+        ((uintptr_t)y_pad & 15) || ((uintptr_t)c_pad & 15) || ((uintptr_t)y_org & 3) || ((uintptr_t)c_org & 3))
+        return PMCTF_EINVAL;
+    const unsigned groups_y = (unsigned)(((long)Hp * Wp + 3) / 4), groups_c = (unsigned)((2L * (Hp >> 1) * (Wp >> 1) + 3) / 4);
+    const float down = 1.0f / (float)(1 << (bitdepth - 8));
+    PM_LAUNCH(yuv420_to_planes_kernel<S>, grid_of((long)groups_y + groups_c), dim3(P_THREADS), 0, (hipStream_t)stream, src,
+              y_pad, c_pad, y_org, c_org, Hp, Wp, h, w, down, groups_y, groups_c);
+    return pm_launch_status();
 }
 
 extern "C" int pmctf_yuv420_u8_to_planes_f32(const uint8_t *src, float *y_pad, float *c_pad, float *y_org, float *c_org,
                                              int Hp, int Wp, int h, int w, void *stream) {
-    if (!src || !y_pad || !c_pad || !size_ok(h, w) || !padded_ok(Hp, Wp, h, w) || ((uintptr_t)y_pad & 15) ||
-        ((uintptr_t)c_pad & 15) || ((uintptr_t)y_org & 3) || ((uintptr_t)c_org & 3))
-        return PMCTF_EINVAL;
-    const unsigned groups_y = (unsigned)(((long)Hp * Wp + 3) / 4), groups_c = (unsigned)((2L * (Hp >> 1) * (Wp >> 1) + 3) / 4);
-    PM_LAUNCH(yuv420_u8_to_planes_kernel, grid_of((long)groups_y + groups_c), dim3(P_THREADS), 0, (hipStream_t)stream, src,
-              y_pad, c_pad, y_org, c_org, Hp, Wp, h, w, groups_y, groups_c);
-    return pm_launch_status();
+    return yuv420_to_planes<uint8_t>(src, y_pad, c_pad, y_org, c_org, Hp, Wp, h, w, 8, stream);
+}
+
+extern "C" int pmctf_yuv420_u16_to_planes_f32(const uint16_t *src, float *y_pad, float *c_pad, float *y_org, float *c_org,
+                                              int Hp, int Wp, int h, int w, int bitdepth, void *stream) {
+    if (!depth_ok(bitdepth)) return PMCTF_EINVAL;
+    return yuv420_to_planes<uint16_t>(src, y_pad, c_pad, y_org, c_org, Hp, Wp, h, w, bitdepth, stream);
 }
 
 // ------------------------------------------------------------------------------------------- (c) RGB -> YUV 4:2:0 bytes
@@ -232,4 +252,67 @@ extern "C" int pmctf_rgb8_to_yuv420_u8(const uint8_t *rgb, uint8_t *yuv, int h, 
     PM_LAUNCH(rgb8_to_yuv420_u8_kernel, grid_of((long)(h >> 1) * ((w + 3) >> 2)), dim3(P_THREADS), 0, (hipStream_t)stream,
               rgb, yuv, h, w);
     return pm_launch_status();
+}
+
+// ------------------------------------------------------------------------------------- (d) float planes -> sample planes
+// Padded planes [N][Hp][Wp] -> cropped [N][h][w], one flat array of samples rint(clamp(x * up, 0, top)) with up = 2^(b - 8),
+// top = 2^b - 1: a thread makes four consecutive ones (they may straddle a row end when w % 4 != 0) and stores them as
+// wide as their address allows; the last total % 4 samples are written one by one.
+__device__ __forceinline__ unsigned px_sample(const float *__restrict__ x, unsigned i, int h, int w, int Hp, int Wp, float up,
+                                              float top) {
+    const unsigned row = i / (unsigned)w, col = i - row * (unsigned)w;
+    const unsigned n = row / (unsigned)h, y = row - n * (unsigned)h;
+    return round_sample(x[((size_t)n * (unsigned)Hp + y) * (unsigned)Wp + col], up, top);
+}
+
+template <typename S>
+__global__ __launch_bounds__(P_THREADS) void planes_to_samples_kernel(const float *__restrict__ x, S *__restrict__ out,
+                                                                       unsigned total, int Hp, int Wp, int h, int w, float up,
+                                                                       float top) {
+    const unsigned quads = total >> 2;
+    const unsigned q = blockIdx.x * P_THREADS + threadIdx.x;
+    if (q < quads) {
+        const unsigned i = q << 2;
+        unsigned v[4];
+        const unsigned row = i / (unsigned)w, col = i - row * (unsigned)w;
+        if (col + 3 < (unsigned)w) {                 // one row: one address computation, the loads side by side
+            const unsigned n = row / (unsigned)h, y = row - n * (unsigned)h;
+            const float *p = x + ((size_t)n * (unsigned)Hp + y) * (unsigned)Wp + col;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = round_sample(p[k], up, top);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = px_sample(x, i + k, h, w, Hp, Wp, up, top);
+        }
+        store4(out + i, v, 4);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (total & 3u)) {
+        const unsigned i = (quads << 2) + threadIdx.x;
+        out[i] = (S)px_sample(x, i, h, w, Hp, Wp, up, top);
+    }
+}
+
+// A plane tensor may be the chroma of a picture whose half size is odd (6x10 -> 3x5): odd sizes are valid here.  Each entry
+// adds its own refusals; N * Hp * Wp <= 2^31 - 1 keeps every flat index of the kernel on 32 bits.
+template <typename S>
+static int planes_to_samples(const float *x, S *out, int N, int Hp, int Wp, int h, int w, int bitdepth, void *stream) {
+    if (!x || !out || N <= 0 || h <= 0 || w <= 0 || h > Hp || w > Wp) return PMCTF_EINVAL;
+    const unsigned total = (unsigned)((long)N * h * w);
+    const float up = (float)(1 << (bitdepth - 8)), top = (float)((1 << bitdepth) - 1);
+    PM_LAUNCH(planes_to_samples_kernel<S>, grid_of(((long)total + 3) / 4), dim3(P_THREADS), 0, (hipStream_t)stream, x, out,
+              total, Hp, Wp, h, w, up, top);
+    return pm_launch_status();
+}
+
+extern "C" int pmctf_planes_to_u8(const float *x, uint8_t *out, int N, int Hp, int Wp, int h, int w, void *stream) {
+    if ((long)N * Hp * Wp > 0x7fffffffL) return PMCTF_EINVAL;          // no side limit, no alignment asked of out
+    return planes_to_samples<uint8_t>(x, out, N, Hp, Wp, h, w, 8, stream);
+}
+
+extern "C" int pmctf_planes_to_u16(const float *x, uint16_t *out, int N, int Hp, int Wp, int h, int w, int bitdepth,
+                                   void *stream) {
+    if (Hp > P_MAX_SIDE || Wp > P_MAX_SIDE || !depth_ok(bitdepth) || ((uintptr_t)x & 3) || ((uintptr_t)out & 1) ||
+        (long)N * Hp * Wp > 0x7fffffffL)
+        return PMCTF_EINVAL;
+    return planes_to_samples<uint16_t>(x, out, N, Hp, Wp, h, w, bitdepth, stream);
 }

@@ -2,7 +2,7 @@
 // size) and picture_chroma.hip (chroma planes to another chroma format).  Per plane, with max = 2^b - 1:
 //     horizontal  t   = (sum_k coef_x[ox][k] * src[r][min(start_x[ox] + k, w_in - 1)] + 32) >> 6             (int32)
 //     vertical    out = clamp((sum_k coef_y[oy][k] * t[min(start_y[oy] + k, h_in - 1)][ox] + 2^21) >> 22, 0, max)   (int64)
-// A workgroup of S_THREADS threads owns a tile of S_TH x S_TW output samples.  It makes the horizontal pass of the source
+// A workgroup of P_THREADS threads owns a tile of S_TH x S_TW output samples.  It makes the horizontal pass of the source
 // rows the tile needs into LDS (int32, row stride S_TW: lane i of a wave touches bank i, no conflicts) and the vertical
 // pass from there, one thread per four neighbouring outputs (one 16-byte LDS read per tap).  Nothing intermediate goes to
 // HBM.  Every index read from a table is clamped before use (source column and row, LDS row): a wrong table gives wrong
@@ -12,20 +12,20 @@
 // one gives 256 x, the vertical one (t + 128) >> 8, clamped), so the template flags IDX / IDY compute just that without
 // reading a table.
 //
-// Accesses take the widest form the address allows, as picture_hbd.hip does: planes of a packed picture start on odd
+// Accesses take the widest form the address allows, as picture_ops.hip does: planes of a packed picture start on odd
 // byte (u8) or halfword (u16) boundaries.  A thread reads its window of a source row as aligned 32-bit words where the
-// window holds whole ones and sample by sample at its ends, and stores its four outputs as one word (u8), or as 8 bytes
-// or two words (u16), when they lie in one row at such an address; sample by sample otherwise.
+// window holds whole ones and sample by sample at its ends, and stores its four outputs with store4 (picture_common.h):
+// one word (u8), or 8 bytes or two words (u16), when they lie in one row at such an address; sample by sample otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define S_THREADS 256
+#include "picture_common.h"
+
 #define S_TW 64                                  // tile width in output samples
 #define S_TH 16                                  // tile height
 #define S_ROWS 80                                // source rows of one tile held in LDS
 #define S_TAPS 20                                // longest table row accepted (the 4:1 limit needs 17)
-#define S_MAX_SIDE 16384
 
 struct ScalePlane {
     int h_in, w_in, h_out, w_out;
@@ -66,31 +66,6 @@ __device__ __forceinline__ int window_sum(const uint16_t *__restrict__ s, int n,
     return acc;
 }
 
-// four neighbouring outputs of one row, `cols` of them inside the plane
-__device__ __forceinline__ void store4(uint8_t *__restrict__ o, const unsigned v[4], int cols) {
-    if (cols >= 4 && !((uintptr_t)o & 3)) {
-        *reinterpret_cast<uint32_t *>(o) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < cols) o[k] = (uint8_t)v[k];
-    }
-}
-
-__device__ __forceinline__ void store4(uint16_t *__restrict__ o, const unsigned v[4], int cols) {
-    const unsigned lo = v[0] | (v[1] << 16), hi = v[2] | (v[3] << 16);
-    if (cols >= 4 && !((uintptr_t)o & 7)) {
-        *reinterpret_cast<uint2 *>(o) = make_uint2(lo, hi);
-    } else if (cols >= 4 && !((uintptr_t)o & 3)) {
-        reinterpret_cast<uint32_t *>(o)[0] = lo;
-        reinterpret_cast<uint32_t *>(o)[1] = hi;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < cols) o[k] = (uint16_t)v[k];
-    }
-}
-
 // one tile of plane P; tmp: S_ROWS * S_TW ints of LDS, 16-byte aligned, cx: S_TAPS * S_TW ints of LDS.  The whole
 // workgroup calls it (it synchronises).  IDX / IDY: that axis keeps its length, its table is not read.
 template <typename S, bool IDX, bool IDY>
@@ -113,7 +88,7 @@ __device__ __forceinline__ void resample_tile(const S *__restrict__ src, S *__re
 
     if constexpr (!IDX) {
         // x coefficients of the tile's columns, tap-major: cx[k][column]; zero past the plane's last column
-        for (int i = tid; i < P.tx * S_TW; i += S_THREADS) {
+        for (int i = tid; i < P.tx * S_TW; i += P_THREADS) {
             const int k = i / S_TW, col = i - k * S_TW;
             cx[i] = ox0 + col < P.w_out ? (int)P.coef_x[(size_t)(ox0 + col) * P.tx + k] : 0;
         }
@@ -127,12 +102,12 @@ __device__ __forceinline__ void resample_tile(const S *__restrict__ src, S *__re
         const S *plane = src + P.in_off;
         if constexpr (IDX) {
             const int xs = live ? min(ox0 + col, P.w_in - 1) : 0;
-            for (int r = tid / S_TW; r < nrows; r += S_THREADS / S_TW)
+            for (int r = tid / S_TW; r < nrows; r += P_THREADS / S_TW)
                 tmp[r * S_TW + col] = live ? (int)plane[(size_t)(r0 + r) * (unsigned)P.w_in + xs] << 8 : 0;
         } else {
             const int xs = live ? clampi(P.start_x[ox0 + col], 0, P.w_in - 1) : 0;
             const int n = live ? min(P.tx, P.w_in - xs) : 0;        // taps past the row's end have zero coefficients
-            for (int r = tid / S_TW; r < nrows; r += S_THREADS / S_TW) {
+            for (int r = tid / S_TW; r < nrows; r += P_THREADS / S_TW) {
                 const S *s = plane + (size_t)(r0 + r) * (unsigned)P.w_in + xs;
                 tmp[r * S_TW + col] = (window_sum(s, n, cx + col) + 32) >> 6;
             }

@@ -24,7 +24,7 @@ struct ScaleArgs {
 };
 
 template <typename S>
-__global__ __launch_bounds__(S_THREADS) void resize_yuv420_kernel(const S *__restrict__ src, S *__restrict__ dst,
+__global__ __launch_bounds__(P_THREADS) void resize_yuv420_kernel(const S *__restrict__ src, S *__restrict__ dst,
                                                                    const ScaleArgs a, int top) {
     __shared__ __attribute__((aligned(16))) int tmp[S_ROWS * S_TW];
     __shared__ int cx[S_TAPS * S_TW];
@@ -44,7 +44,6 @@ __global__ __launch_bounds__(S_THREADS) void resize_yuv420_kernel(const S *__res
     resample_tile<S, false, false>(src, dst, P, tile, top, tmp, cx);
 }
 
-static bool side_ok(int n) { return n > 0 && !(n & 1) && n <= S_MAX_SIDE; }
 static bool ratio_ok(int n_in, int n_out) { return 4L * n_out >= n_in && n_out <= 4L * n_in; }
 static bool taps_ok(int t) { return t >= 1 && t <= S_TAPS; }
 
@@ -66,7 +65,7 @@ static int resize_yuv420(const S *src, S *dst, int h_in, int w_in, int h_out, in
     set_plane(a.p[1], hci, wci, hco, wco, chroma_x, taps[2], chroma_y, taps[3], ny_in, ny_out);
     set_plane(a.p[2], hci, wci, hco, wco, chroma_x, taps[2], chroma_y, taps[3], ny_in + nc_in, ny_out + nc_out);
     const unsigned blocks = a.p[0].tiles + a.p[1].tiles + a.p[2].tiles;
-    PM_LAUNCH(resize_yuv420_kernel<S>, dim3(blocks), dim3(S_THREADS), 0, (hipStream_t)stream, src, dst, a,
+    PM_LAUNCH(resize_yuv420_kernel<S>, dim3(blocks), dim3(P_THREADS), 0, (hipStream_t)stream, src, dst, a,
               (1 << bitdepth) - 1);
     return pm_launch_status();
 }
@@ -81,7 +80,7 @@ extern "C" int pmctf_resize_yuv420_u8(const uint8_t *src, uint8_t *dst, int h_in
 extern "C" int pmctf_resize_yuv420_u16(const uint16_t *src, uint16_t *dst, int h_in, int w_in, int h_out, int w_out,
                                        const void *luma_x, const void *luma_y, const void *chroma_x, const void *chroma_y,
                                        const int taps[4], int bitdepth, void *stream) {
-    if (bitdepth < 9 || bitdepth > 16) return PMCTF_EINVAL;
+    if (!depth_ok(bitdepth)) return PMCTF_EINVAL;
     return resize_yuv420<uint16_t>(src, dst, h_in, w_in, h_out, w_out, luma_x, luma_y, chroma_x, chroma_y, taps, bitdepth,
                                    stream);
 }

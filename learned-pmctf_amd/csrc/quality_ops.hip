@@ -15,9 +15,9 @@
 
 #include "../../include/pmctf_hip.h"
 #include "launch.h"
+#include "picture_common.h"
 #include "picture_math.h"
 
-#define Q_THREADS 256
 #define Q_FRONT_BLOCKS 1024                      // partial sums of the front end: [Q_FRONT_BLOCKS][4] doubles
 #define Q_TILE 32                                // MS-SSIM output tile (Q_TILE x Q_TILE per workgroup)
 #define Q_TAPS 11
@@ -26,9 +26,8 @@
 #define Q_RUN 4                                  // consecutive outputs per thread in either pass
 #define Q_SPAN (Q_RUN + Q_TAPS - 1)              // 14: samples behind Q_RUN outputs
 #define Q_SCALES 5
-#define Q_MAX_SIDE 16384
 
-static_assert(Q_THREADS * Q_RUN == Q_TILE * Q_TILE && Q_TILE % Q_RUN == 0 && Q_STRIDE % 4 == 0 &&
+static_assert(P_THREADS * Q_RUN == Q_TILE * Q_TILE && Q_TILE % Q_RUN == 0 && Q_STRIDE % 4 == 0 &&
               Q_STRIDE >= Q_TILE - Q_RUN + 16, "tile shape: one column run per thread, 16-byte rows, four float4 per run");
 static_assert(PMCTF_QUALITY_FRONT_FLOATS == 2 * 4 * Q_FRONT_BLOCKS, "front-end partial sums: header and kernel disagree");
 static_assert(PMCTF_QUALITY_OUT_DOUBLES == 4 + 2 * 3 * Q_SCALES, "result layout: header and kernel disagree");
@@ -37,27 +36,15 @@ struct QWindow {
     float g[Q_TAPS];
 };
 
-// sum over the workgroup, the same value in every thread; fixed order.  `buf` holds Q_THREADS / 64 values.
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T *buf) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                             // buf may still be read from the previous call
-    if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = buf[0];
-    for (int i = 1; i < Q_THREADS / 64; ++i) s += buf[i];
-    return s;
-}
-
-__global__ __launch_bounds__(Q_THREADS) void quality_front_kernel(
+__global__ __launch_bounds__(P_THREADS) void quality_front_kernel(
     const float *__restrict__ rec_y, const float *__restrict__ rec_c, const float *__restrict__ org_y,
     const float *__restrict__ org_c, int Hp, int Wp, int h, int w, float *__restrict__ rgb_rec,
     float *__restrict__ rgb_org, double *__restrict__ partial) {
-    __shared__ double red[Q_THREADS / 64];
+    __shared__ double red[P_THREADS / 64];
     const int hc = h >> 1, wc = w >> 1, Wc = Wp >> 1;
     const long plane_p = (long)(Hp >> 1) * Wc, plane_o = (long)hc * wc, n = (long)h * w;
     double sy = 0.0, scb = 0.0, scr = 0.0, srgb = 0.0;
-    for (long i = (long)blockIdx.x * Q_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * Q_THREADS) {
+    for (long i = (long)blockIdx.x * P_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * P_THREADS) {
         const int y = (int)((unsigned)i / (unsigned)w), x = (int)((unsigned)i % (unsigned)w);
         const float ry = round_u8(rec_y[(long)y * Wp + x]), oy = org_y[i];
         sy += (double)((ry - oy) * (ry - oy));
@@ -103,13 +90,13 @@ __global__ __launch_bounds__(Q_THREADS) void quality_front_kernel(
 // Q_TILE x Q_TILE tiles: a workgroup forms the map values whose window starts in its tile (those inside the (H-10)x(W-10)
 // valid region) and the pooled samples (Q_TILE/2)^2 of its tile; blockIdx.z is the channel, so that the small scales, a
 // handful of tiles each, are not three channels deep in one workgroup.  partial: [tiles][3][2] sums of cs and ssim.
-__global__ __launch_bounds__(Q_THREADS) void msssim_scale_kernel(
+__global__ __launch_bounds__(P_THREADS) void msssim_scale_kernel(
     const float *__restrict__ x, const float *__restrict__ y, int H, int W, float *__restrict__ nx,
     float *__restrict__ ny, int Hn, int Wn, int pad_h, int pad_w, QWindow win, double *__restrict__ partial) {
     __shared__ __attribute__((aligned(16))) float xs[Q_HALO * Q_STRIDE], ys[Q_HALO * Q_STRIDE];
     __shared__ __attribute__((aligned(16))) float mom[5][Q_HALO * Q_TILE];
-    __shared__ float redf[Q_THREADS / 64];
-    __shared__ double redd[Q_THREADS / 64];
+    __shared__ float redf[P_THREADS / 64];
+    __shared__ double redd[P_THREADS / 64];
     const int tid = threadIdx.x, ty0 = blockIdx.y * Q_TILE, tx0 = blockIdx.x * Q_TILE;
     const long plane = (long)H * W;
     const int rows_in = min(Q_HALO, H - ty0), cols_in = min(Q_HALO, W - tx0);
@@ -119,11 +106,11 @@ __global__ __launch_bounds__(Q_THREADS) void msssim_scale_kernel(
     const float *xp = x + c * plane, *yp = y + c * plane;
     {
         // every load of the tile is issued before the first one is used: one memory latency per tile, not one per element
-        constexpr int PER = (Q_HALO * Q_HALO + Q_THREADS - 1) / Q_THREADS;
+        constexpr int PER = (Q_HALO * Q_HALO + P_THREADS - 1) / P_THREADS;
         float a[PER], b[PER], local = 0.0f;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
-            const int i = tid + k * Q_THREADS, r = i / Q_HALO, cc = i - r * Q_HALO;
+            const int i = tid + k * P_THREADS, r = i / Q_HALO, cc = i - r * Q_HALO;
             const bool in = r < rows_in && cc < cols_in;          // r >= Q_HALO past the tile: rows_in <= Q_HALO
             a[k] = in ? xp[(long)(ty0 + r) * W + tx0 + cc] : 0.0f;
             b[k] = in ? yp[(long)(ty0 + r) * W + tx0 + cc] : 0.0f;
@@ -136,13 +123,13 @@ __global__ __launch_bounds__(Q_THREADS) void msssim_scale_kernel(
         const float shift = rintf(block_sum(local, redf) / (float)(rows_in * cols_in));
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
-            const int i = tid + k * Q_THREADS, r = i / Q_HALO, cc = i - r * Q_HALO;
+            const int i = tid + k * P_THREADS, r = i / Q_HALO, cc = i - r * Q_HALO;
             if (i < Q_HALO * Q_HALO) { xs[r * Q_STRIDE + cc] = a[k] - shift; ys[r * Q_STRIDE + cc] = b[k] - shift; }
         }
         __syncthreads();
         // Row pass: a thread takes Q_RUN consecutive outputs of one row, so that the Q_SPAN samples behind them are read
         // from LDS once (16-byte reads) instead of Q_TAPS times each.  Every output still adds its taps in the order 0..10.
-        for (int it = tid; it < Q_HALO * (Q_TILE / Q_RUN); it += Q_THREADS) {
+        for (int it = tid; it < Q_HALO * (Q_TILE / Q_RUN); it += P_THREADS) {
             const int r = it / (Q_TILE / Q_RUN), col = (it % (Q_TILE / Q_RUN)) * Q_RUN;
             const float4 *xr = reinterpret_cast<const float4 *>(xs + r * Q_STRIDE + col);
             const float4 *yr = reinterpret_cast<const float4 *>(ys + r * Q_STRIDE + col);
@@ -241,13 +228,13 @@ struct QSegments {
 
 // one workgroup per segment and column: thread t adds rows t, t + 256, ... in that order, then the workgroup adds its
 // threads
-__global__ __launch_bounds__(Q_THREADS) void quality_finish_kernel(QSegments segs) {
-    __shared__ double red[Q_THREADS / 64];
+__global__ __launch_bounds__(P_THREADS) void quality_finish_kernel(QSegments segs) {
+    __shared__ double red[P_THREADS / 64];
     const QSegment sg = segs.s[blockIdx.x];
     const int k = blockIdx.y;
     if (k >= sg.width) return;
     double v = 0.0;
-    for (int r = threadIdx.x; r < sg.rows; r += Q_THREADS) v += sg.src[(long)r * sg.width + k];
+    for (int r = threadIdx.x; r < sg.rows; r += P_THREADS) v += sg.src[(long)r * sg.width + k];
     v = block_sum(v, red);
     if (threadIdx.x == 0) sg.dst[k] = sg.scale * v;
 }
@@ -261,7 +248,6 @@ struct QLayout {
     long total_floats;
 };
 
-static bool size_ok(int h, int w) { return h > 0 && w > 0 && !((h | w) & 1) && h <= Q_MAX_SIDE && w <= Q_MAX_SIDE; }
 
 static QLayout layout_for(int h, int w) {
     QLayout L;
@@ -304,18 +290,18 @@ extern "C" int64_t pmctf_msssim_scratch_floats(int h, int w) {
 extern "C" int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, const float *org_y, const float *org_c,
                                        int Hp, int Wp, int h, int w, int msssim, float *scratch, double *out,
                                        void *stream) {
-    if (!rec_y || !rec_c || !org_y || !org_c || !scratch || !out || !size_ok(h, w) || h > Hp || w > Wp || ((Hp | Wp) & 1) ||
-        Hp > Q_MAX_SIDE || Wp > Q_MAX_SIDE || ((uintptr_t)scratch & 7) || ((uintptr_t)out & 7))
+    if (!rec_y || !rec_c || !org_y || !org_c || !scratch || !out || !size_ok(h, w) || !padded_ok(Hp, Wp, h, w) ||
+        ((uintptr_t)scratch & 7) || ((uintptr_t)out & 7))
         return PMCTF_EINVAL;
     if (msssim && (h < w ? h : w) <= (Q_TAPS - 1) * (1 << (Q_SCALES - 1))) return PMCTF_EINVAL;
     const hipStream_t st = (hipStream_t)stream;
     const QLayout L = layout_for(h, w);
     double *partial = (double *)scratch;
     const long n = (long)h * w;
-    const int blocks = (int)((n + Q_THREADS - 1) / Q_THREADS < Q_FRONT_BLOCKS ? (n + Q_THREADS - 1) / Q_THREADS : Q_FRONT_BLOCKS);
+    const int blocks = (int)((n + P_THREADS - 1) / P_THREADS < Q_FRONT_BLOCKS ? (n + P_THREADS - 1) / P_THREADS : Q_FRONT_BLOCKS);
     float *rgb_rec = msssim ? scratch + L.plane_off[0] : nullptr;
     float *rgb_org = msssim ? rgb_rec + 3 * n : nullptr;
-    PM_LAUNCH(quality_front_kernel, dim3(blocks), dim3(Q_THREADS), 0, st, rec_y, rec_c, org_y, org_c, Hp, Wp, h, w, rgb_rec,
+    PM_LAUNCH(quality_front_kernel, dim3(blocks), dim3(P_THREADS), 0, st, rec_y, rec_c, org_y, org_c, Hp, Wp, h, w, rgb_rec,
               rgb_org, partial);
     int rc = pm_launch_status();
     if (rc) return rc;
@@ -329,7 +315,7 @@ extern "C" int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, c
             const bool last = s == Q_SCALES - 1;
             float *nx = last ? nullptr : scratch + L.plane_off[s + 1];
             float *ny = last ? nullptr : nx + 3L * L.H[s + 1] * L.W[s + 1];
-            PM_LAUNCH(msssim_scale_kernel, dim3(L.tiles_x[s], L.tiles_y[s], 3), dim3(Q_THREADS), 0, st, x, y, L.H[s], L.W[s], nx,
+            PM_LAUNCH(msssim_scale_kernel, dim3(L.tiles_x[s], L.tiles_y[s], 3), dim3(P_THREADS), 0, st, x, y, L.H[s], L.W[s], nx,
                       ny, last ? 0 : L.H[s + 1], last ? 0 : L.W[s + 1], L.pad_h[s], L.pad_w[s], win,
                       partial + L.partial_off[s]);
             rc = pm_launch_status();
@@ -338,6 +324,6 @@ extern "C" int pmctf_frame_quality_f32(const float *rec_y, const float *rec_c, c
                               1.0 / ((double)(L.H[s] - (Q_TAPS - 1)) * (double)(L.W[s] - (Q_TAPS - 1)))};
         }
     }
-    PM_LAUNCH(quality_finish_kernel, dim3(nseg, 6), dim3(Q_THREADS), 0, st, segs);
+    PM_LAUNCH(quality_finish_kernel, dim3(nseg, 6), dim3(P_THREADS), 0, st, segs);
     return pm_launch_status();
 }

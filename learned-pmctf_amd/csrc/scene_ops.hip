@@ -14,17 +14,13 @@
 
 #include "../../include/pmctf_hip.h"
 #include "launch.h"
+#include "picture_common.h"
 
-#define S_THREADS 256
-#define S_WAVES (S_THREADS / 64)
+#define S_WAVES (P_THREADS / 64)
 #define S_BINS 256
-#define S_MAX_SIDE 16384                         // a plane has at most 2^28 samples: flat indices fit 32 bits
 #define S_MAX_BLOCKS 2048                        // grid cap: the rest is a grid-stride loop
 
-// rint(clamp(x * up, 0, 65535)): fmaxf returns its other operand for a NaN, which so becomes 0
-__device__ __forceinline__ unsigned luma_u16(float x, float up) {
-    return (unsigned)(int)rintf(fminf(fmaxf(x * up, 0.0f), 65535.0f));
-}
+__device__ __forceinline__ unsigned luma_u16(float x, float up) { return round_sample(x, up, 65535.0f); }
 
 __device__ __forceinline__ void count(uint32_t *wave_hist, unsigned u, int shift) {
     const unsigned bin = u >> shift;
@@ -33,7 +29,7 @@ __device__ __forceinline__ void count(uint32_t *wave_hist, unsigned u, int shift
 
 __device__ __forceinline__ uint64_t abs_diff(unsigned a, unsigned b) { return (uint64_t)(a > b ? a - b : b - a); }
 
-__global__ __launch_bounds__(S_THREADS) void luma_activity_kernel(const float *__restrict__ cur, const float *__restrict__ prev,
+__global__ __launch_bounds__(P_THREADS) void luma_activity_kernel(const float *__restrict__ cur, const float *__restrict__ prev,
                                                                    unsigned total, float up, int shift,
                                                                    uint32_t *__restrict__ hist256,
                                                                    unsigned long long *__restrict__ sad) {
@@ -45,7 +41,7 @@ __global__ __launch_bounds__(S_THREADS) void luma_activity_kernel(const float *_
     uint32_t *mine = hist[threadIdx.x >> 6];
     uint64_t s = 0;
     const unsigned quads = total >> 2;
-    for (unsigned q = blockIdx.x * S_THREADS + threadIdx.x; q < quads; q += gridDim.x * S_THREADS) {
+    for (unsigned q = blockIdx.x * P_THREADS + threadIdx.x; q < quads; q += gridDim.x * P_THREADS) {
         const float4 c = reinterpret_cast<const float4 *>(cur)[q];
         const unsigned u[4] = {luma_u16(c.x, up), luma_u16(c.y, up), luma_u16(c.z, up), luma_u16(c.w, up)};
 #pragma unroll
@@ -67,22 +63,17 @@ __global__ __launch_bounds__(S_THREADS) void luma_activity_kernel(const float *_
 #pragma unroll
     for (int k = 0; k < S_WAVES; ++k) n += hist[k][threadIdx.x];
     if (n) atomicAdd(hist256 + threadIdx.x, n);
-    if (prev) {                                                     // uniform over the launch
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down((unsigned long long)s, off, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = red[0];
-            for (int k = 1; k < S_WAVES; ++k) t += red[k];
-            if (t) atomicAdd(sad, (unsigned long long)t);
-        }
+    if (prev) {                                  // uniform over the launch
+        // block_sum's leading barrier guards a reuse of red; red is used once here, so that barrier is harmless, not needed
+        const uint64_t t = block_sum(s, red);
+        if (threadIdx.x == 0 && t) atomicAdd(sad, (unsigned long long)t);
     }
 }
 
 extern "C" int pmctf_luma_activity_f32(const float *cur, const float *prev, int h, int w, int bitdepth, uint32_t *hist256,
                                        uint64_t *sad, void *stream) {
-    if (!cur || !hist256 || (prev && !sad) || bitdepth < 8 || bitdepth > 16 || h < 1 || w < 1 || h > S_MAX_SIDE ||
-        w > S_MAX_SIDE || (((uintptr_t)cur | (uintptr_t)prev) & 15) || ((uintptr_t)hist256 & 3) || ((uintptr_t)sad & 7))
+    if (!cur || !hist256 || (prev && !sad) || bitdepth < 8 || bitdepth > 16 || h < 1 || w < 1 || h > P_MAX_SIDE ||
+        w > P_MAX_SIDE || (((uintptr_t)cur | (uintptr_t)prev) & 15) || ((uintptr_t)hist256 & 3) || ((uintptr_t)sad & 7))
         return PMCTF_EINVAL;
     const hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
@@ -93,9 +84,9 @@ extern "C" int pmctf_luma_activity_f32(const float *cur, const float *prev, int 
         return -2;
     }
     const unsigned total = (unsigned)((long)h * w);
-    const long blocks = ((long)(total >> 2) + S_THREADS - 1) / S_THREADS;
+    const long blocks = ((long)(total >> 2) + P_THREADS - 1) / P_THREADS;
     const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks < S_MAX_BLOCKS ? blocks : S_MAX_BLOCKS));
-    PM_LAUNCH(luma_activity_kernel, dim3(grid), dim3(S_THREADS), 0, st, cur, prev, total, (float)(1 << (bitdepth - 8)),
+    PM_LAUNCH(luma_activity_kernel, dim3(grid), dim3(P_THREADS), 0, st, cur, prev, total, (float)(1 << (bitdepth - 8)),
               bitdepth - 8, hist256, (unsigned long long *)sad);
     return pm_launch_status();
 }

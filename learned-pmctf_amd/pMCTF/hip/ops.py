@@ -603,7 +603,7 @@ def frame_quality(rec_y, rec_c, org_y, org_c, h, w, msssim=True, return_means=Fa
 
 
 # ------------------------------------------------------------------------------------------------
-# pictures in and out (csrc/picture_ops.hip)
+# pictures in and out (csrc/picture_ops.hip); 16-bit samples travel as torch.uint16
 PICTURE_MAX_SIDE = 16384
 
 
@@ -641,22 +641,22 @@ def frame_to_rgb8(rec_y, rec_c, h, w):
     return out
 
 
-def planes_from_u8(frame_u8, h, w, psize=128, originals=True):
-    """One picture as it lies in a planar 8-bit 4:2:0 file (uint8 device tensor of h*w*3/2 bytes) -> (y_pad (1,1,Hp,Wp),
-    c_pad (2,1,Hp/2,Wp/2), y_org (1,1,h,w), c_org (2,1,h/2,w/2)) float32: the model's inputs, zero padded right / bottom to
-    multiples of psize, and the un-padded originals (None, None with originals=False).  One launch; the counterpart of
-    planes_to_u8."""
+def _planes_from(frame, h, w, bitdepth, psize, originals):
+    """the body of planes_from_u8 (bitdepth None: bytes) and planes_from_u16 (9..16: 16-bit samples)"""
     from ..utils.stream_helper import get_padding_size
     h, w = _picture_size(h, w)
+    dtype, word, unit = (torch.uint8, "uint8", "bytes") if bitdepth is None else (torch.uint16, "uint16", "samples")
+    if bitdepth is not None:
+        bitdepth = _bitdepth(bitdepth)
     psize = int(psize)
     if psize <= 0 or psize & 1:
         raise ValueError(f"psize must be even and positive (got {psize})")
-    if not isinstance(frame_u8, torch.Tensor) or frame_u8.dtype != torch.uint8:
-        raise ValueError("expect a uint8 tensor")
-    if frame_u8.numel() != h * w * 3 // 2:
-        raise ValueError(f"a {h}x{w} 4:2:0 picture has {h * w * 3 // 2} bytes, got {frame_u8.numel()}")
-    dev = _dev(frame_u8)
-    frame_u8 = frame_u8.contiguous()
+    if not isinstance(frame, torch.Tensor) or frame.dtype != dtype:
+        raise ValueError(f"expect a {word} tensor")
+    if frame.numel() != h * w * 3 // 2:
+        raise ValueError(f"a {h}x{w} 4:2:0 picture has {h * w * 3 // 2} {unit}, got {frame.numel()}")
+    dev = _dev(frame)
+    frame = frame.contiguous()
     _, right, _, bottom = get_padding_size(h, w, p=psize)
     Hp, Wp = h + bottom, w + right
     if max(Hp, Wp) > PICTURE_MAX_SIDE:
@@ -665,9 +665,38 @@ def planes_from_u8(frame_u8, h, w, psize=128, originals=True):
     c_pad = torch.empty((2, 1, Hp // 2, Wp // 2), dtype=torch.float32, device=dev)
     y_org = torch.empty((1, 1, h, w), dtype=torch.float32, device=dev) if originals else None
     c_org = torch.empty((2, 1, h // 2, w // 2), dtype=torch.float32, device=dev) if originals else None
-    _lib.check(_lib.hip().pmctf_yuv420_u8_to_planes_f32(_pu8(frame_u8), _p(y_pad), _p(c_pad), _p(y_org), _p(c_org), Hp, Wp,
-                                                        h, w, _stream()), "planes_from_u8")
+    planes = (_p(y_pad), _p(c_pad), _p(y_org), _p(c_org), Hp, Wp, h, w)
+    if bitdepth is None:
+        _lib.check(_lib.hip().pmctf_yuv420_u8_to_planes_f32(_pu8(frame), *planes, _stream()), "planes_from_u8")
+    else:
+        _lib.check(_lib.hip().pmctf_yuv420_u16_to_planes_f32(_pu16(frame), *planes, bitdepth, _stream()), "planes_from_u16")
     return y_pad, c_pad, y_org, c_org
+
+
+def planes_from_u8(frame_u8, h, w, psize=128, originals=True):
+    """One picture as it lies in a planar 8-bit 4:2:0 file (uint8 device tensor of h*w*3/2 bytes) -> (y_pad (1,1,Hp,Wp),
+    c_pad (2,1,Hp/2,Wp/2), y_org (1,1,h,w), c_org (2,1,h/2,w/2)) float32: the model's inputs, zero padded right / bottom to
+    multiples of psize, and the un-padded originals (None, None with originals=False).  One launch; the counterpart of
+    planes_to_u8."""
+    return _planes_from(frame_u8, h, w, None, psize, originals)
+
+
+def planes_from_u16(frame_u16, h, w, bitdepth, psize=128, originals=True):
+    """planes_from_u8 for one picture of a planar 4:2:0 file of `bitdepth` 9..16 (uint16 device tensor of h*w*3/2 samples,
+    as little-endian words lie in the file): every sample v becomes v * 2^-(bitdepth - 8), exactly, so the planes keep the
+    codec's 0..255 range.  -> (y_pad, c_pad, y_org, c_org) float32 as planes_from_u8.  One launch; the counterpart of
+    planes_to_u16."""
+    return _planes_from(frame_u16, h, w, bitdepth, psize, originals)
+
+
+def planes_from(frame, h, w, bitdepth=8, psize=128, originals=True):
+    """planes_from_u8 at bitdepth 8, planes_from_u16 above: with planes_to, the one place that chooses by depth"""
+    return _planes_from(frame, h, w, None if bitdepth == 8 else bitdepth, psize, originals)
+
+
+def planes_to(x, h, w, bitdepth=8):
+    """planes_to_u8 at bitdepth 8, planes_to_u16 above"""
+    return planes_to_u8(x, h, w) if bitdepth == 8 else planes_to_u16(x, h, w, bitdepth)
 
 
 def rgb8_to_yuv420(rgb_u8):
@@ -686,7 +715,7 @@ def rgb8_to_yuv420(rgb_u8):
 
 
 # ------------------------------------------------------------------------------------------------
-# high-bit-depth pictures in and out (csrc/picture_hbd.hip): 16-bit samples travel as torch.uint16
+# high-bit-depth pictures: the uint16_t instantiations of csrc/picture_ops.hip, the error sums of csrc/picture_hbd.hip
 HBD_MIN, HBD_MAX = 9, 16
 
 
@@ -700,36 +729,6 @@ def _bitdepth(bitdepth):
     if not HBD_MIN <= b <= HBD_MAX:
         raise ValueError(f"a 16-bit sample holds a bitdepth of {HBD_MIN}..{HBD_MAX} (got {bitdepth})")
     return b
-
-
-def planes_from_u16(frame_u16, h, w, bitdepth, psize=128, originals=True):
-    """planes_from_u8 for one picture of a planar 4:2:0 file of `bitdepth` 9..16 (uint16 device tensor of h*w*3/2 samples,
-    as little-endian words lie in the file): every sample v becomes v * 2^-(bitdepth - 8), exactly, so the planes keep the
-    codec's 0..255 range.  -> (y_pad, c_pad, y_org, c_org) float32 as planes_from_u8.  One launch; the counterpart of
-    planes_to_u16."""
-    from ..utils.stream_helper import get_padding_size
-    h, w = _picture_size(h, w)
-    bitdepth = _bitdepth(bitdepth)
-    psize = int(psize)
-    if psize <= 0 or psize & 1:
-        raise ValueError(f"psize must be even and positive (got {psize})")
-    if not isinstance(frame_u16, torch.Tensor) or frame_u16.dtype != torch.uint16:
-        raise ValueError("expect a uint16 tensor")
-    if frame_u16.numel() != h * w * 3 // 2:
-        raise ValueError(f"a {h}x{w} 4:2:0 picture has {h * w * 3 // 2} samples, got {frame_u16.numel()}")
-    dev = _dev(frame_u16)
-    frame_u16 = frame_u16.contiguous()
-    _, right, _, bottom = get_padding_size(h, w, p=psize)
-    Hp, Wp = h + bottom, w + right
-    if max(Hp, Wp) > PICTURE_MAX_SIDE:
-        raise ValueError(f"padded size {Hp}x{Wp} exceeds {PICTURE_MAX_SIDE}")
-    y_pad = torch.empty((1, 1, Hp, Wp), dtype=torch.float32, device=dev)
-    c_pad = torch.empty((2, 1, Hp // 2, Wp // 2), dtype=torch.float32, device=dev)
-    y_org = torch.empty((1, 1, h, w), dtype=torch.float32, device=dev) if originals else None
-    c_org = torch.empty((2, 1, h // 2, w // 2), dtype=torch.float32, device=dev) if originals else None
-    _lib.check(_lib.hip().pmctf_yuv420_u16_to_planes_f32(_pu16(frame_u16), _p(y_pad), _p(c_pad), _p(y_org), _p(c_org), Hp,
-                                                         Wp, h, w, bitdepth, _stream()), "planes_from_u16")
-    return y_pad, c_pad, y_org, c_org
 
 
 def planes_to_u16(x, h, w, bitdepth):

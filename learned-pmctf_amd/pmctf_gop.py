@@ -386,10 +386,7 @@ def read_gop_device(reader, gop, device, psize=128):
         h, w = shape
         if resample is not None:
             frame, (h, w) = resample(frame), resample.shape
-        if bitdepth > 8:
-            y_pad, c_pad, y_org, c_org = ops.planes_from_u16(frame, h, w, bitdepth, psize=psize)
-        else:
-            y_pad, c_pad, y_org, c_org = ops.planes_from_u8(frame, h, w, psize=psize)
+        y_pad, c_pad, y_org, c_org = ops.planes_from(frame, h, w, bitdepth, psize=psize)
         orig.append([y_org, c_org])
         padded.append([y_pad, c_pad])
     return padded, orig, size if resample is None else resample.shape
@@ -890,30 +887,29 @@ def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psi
     return {"frames": rec, "frames_coded": coded, "stages": stages}
 
 
-def frames_to_u8(frames_rec, pic_height, pic_width):
-    """reconstructed (padded, float) pictures -> [(Y, Cb, Cr)] uint8 arrays of the un-padded size: one conversion launch
-    per plane tensor (pmctf_planes_to_u8) and one copy of bytes to the host"""
+def frames_to_samples(frames_rec, pic_height, pic_width, bitdepth=8):
+    """reconstructed (padded, float) pictures -> [(Y, Cb, Cr)] arrays of the un-padded size, rint(clamp(x * 2^(bitdepth - 8),
+    0, 2^bitdepth - 1)): uint8 at bitdepth 8, uint16 at 9..16 (write_yuv writes those as the 16-bit file layout).  One
+    conversion launch per plane tensor (ops.planes_to) and one copy of bytes to the host"""
     from pMCTF.hip import ops
     out = []
     for rec_y, rec_c, _ in frames_rec:
-        y = ops.planes_to_u8(rec_y.contiguous(), pic_height, pic_width)
-        c = ops.planes_to_u8(rec_c.contiguous(), pic_height // 2, pic_width // 2)
+        y = ops.planes_to(rec_y.contiguous(), pic_height, pic_width, bitdepth)
+        c = ops.planes_to(rec_c.contiguous(), pic_height // 2, pic_width // 2, bitdepth)
         out.append((y, c))
     host = [(y.cpu().numpy(), c.cpu().numpy()) for y, c in out]
     return [(y[0], c[0], c[1]) for y, c in host]
+
+
+def frames_to_u8(frames_rec, pic_height, pic_width):
+    """frames_to_samples at 8 bits (pmctf_planes_to_u8)"""
+    return frames_to_samples(frames_rec, pic_height, pic_width)
 
 
 def frames_to_u16(frames_rec, pic_height, pic_width, bitdepth):
-    """frames_to_u8 at a bitdepth of 9..16: -> [(Y, Cb, Cr)] uint16 arrays, rint(clamp(x * 2^(bitdepth - 8), 0, 2^bitdepth -
-    1)) of the un-padded size (pmctf_planes_to_u16); write_yuv writes them as the 16-bit file layout"""
+    """frames_to_samples at a bitdepth of 9..16 (pmctf_planes_to_u16); 8 is refused"""
     from pMCTF.hip import ops
-    out = []
-    for rec_y, rec_c, _ in frames_rec:
-        y = ops.planes_to_u16(rec_y.contiguous(), pic_height, pic_width, bitdepth)
-        c = ops.planes_to_u16(rec_c.contiguous(), pic_height // 2, pic_width // 2, bitdepth)
-        out.append((y, c))
-    host = [(y.cpu().numpy(), c.cpu().numpy()) for y, c in out]
-    return [(y[0], c[0], c[1]) for y, c in host]
+    return frames_to_samples(frames_rec, pic_height, pic_width, ops._bitdepth(bitdepth))
 
 
 def frames_to_rgb8(frames_rec, pic_height, pic_width):
@@ -1003,12 +999,8 @@ def picture_hashes(frames_rec, pic_height, pic_width, level, bitdepth=8):
     tensors = []
     for rec_y, rec_c, _ in frames_rec:
         y, c = rec_y.contiguous(), rec_c.contiguous()
-        if bitdepth > 8:
-            c8 = ops.planes_to_u16(c, hc, wc, bitdepth)
-            tensors += [ops.planes_to_u16(y, pic_height, pic_width, bitdepth), c8[0], c8[1]]
-        else:
-            c8 = ops.planes_to_u8(c, hc, wc)
-            tensors += [ops.planes_to_u8(y, pic_height, pic_width), c8[0], c8[1]]
+        c8 = ops.planes_to(c, hc, wc, bitdepth)
+        tensors += [ops.planes_to(y, pic_height, pic_width, bitdepth), c8[0], c8[1]]
         if level == "f32":
             tensors += [y, c]
     crcs = ops.crc32(tensors)
@@ -1151,9 +1143,7 @@ class PlainSink:
         self.shape, self.bitdepth = (height, width), bitdepth             # shape: of every written picture
 
     def pictures(self, frames_rec):
-        if self.bitdepth > 8:
-            return frames_to_u16(frames_rec, *self.shape, self.bitdepth)
-        return frames_to_u8(frames_rec, *self.shape)
+        return frames_to_samples(frames_rec, *self.shape, self.bitdepth)
 
     def rgb8(self, frames_rec):
         return frames_to_rgb8(frames_rec, *self.shape)

@@ -186,12 +186,8 @@ def pack_frame(rec_y, rec_c, h, w, bitdepth=8):
     frames_to_u8 / frames_to_u16 round it"""
     import torch
     from pMCTF.hip import ops
-    if bitdepth > 8:
-        y = ops.planes_to_u16(rec_y.contiguous(), h, w, bitdepth)
-        c = ops.planes_to_u16(rec_c.contiguous(), h // 2, w // 2, bitdepth)
-    else:
-        y = ops.planes_to_u8(rec_y.contiguous(), h, w)
-        c = ops.planes_to_u8(rec_c.contiguous(), h // 2, w // 2)
+    y = ops.planes_to(rec_y.contiguous(), h, w, bitdepth)
+    c = ops.planes_to(rec_c.contiguous(), h // 2, w // 2, bitdepth)
     return torch.cat([y.reshape(-1), c.reshape(-1)])
 
 
@@ -255,10 +251,7 @@ class CodedSize:
         (W, H), (cw, ch), b = self.source, self.coded, self.bitdepth
         sources, self.sources = self.sources[:len(rec)], self.sources[len(rec):]
         assert len(sources) == len(rec), "a reconstructed picture without its source"
-        if b > 8:
-            planes = lambda f: ops.planes_from_u16(f, H, W, b, psize=2)
-        else:
-            planes = lambda f: ops.planes_from_u8(f, H, W, psize=2)
+        planes = lambda f: ops.planes_from(f, H, W, b, psize=2)
         out = []
         for (rec_y, rec_c, *_), src in zip(rec, sources):
             y, c, _, _ = planes(self.up(pack_frame(rec_y, rec_c, ch, cw, b)))

@@ -175,7 +175,7 @@ def specials_plane(shape, seed=7):
     return x
 
 
-# planes_to_u8: rint(clamp(x, 0, 255)) with ties to even; a NaN fails both comparisons of the clamp and converts to 0
+# planes_to_u8: rint(clamp(x, 0, 255)) with ties to even; fmaxf(NaN, 0) is 0, so a NaN becomes 0 by the written clamp
 U8_PATTERNS = [(np.nan, 0), (np.inf, 255), (-np.inf, 0), (0.5, 0), (1.5, 2), (254.5, 254), (255.5, 255), (-0.5, 0),
                (-0.0, 0), (0.0, 0), (2.5, 2), (1e-45, 0), (3.4028235e38, 255), (127.49999, 127), (127.5, 128)]
 

@@ -171,8 +171,7 @@ GUARDS = {
     ("basic_ops.hip", "tiles <= 0x7fffffffL"): [("exempt", "2^31 tiles of 8x32 pixels at 16 channels are 32 TiB of input")],
     ("basic_ops.hip", "(long)H * W * CI_ < 0x7fffffffL"): [("rows", "fewcout_64_1")],
     ("ew_ops.hip", "total < (1L << 31)"): [("rows", "ew_c4", "ew_cfast", "ew_planar")],
-    ("ew_ops.hip", "(long)N * Hp * Wp > 0x7fffffffL"): [("refusal", "planes_to_u8")],
-    ("picture_hbd.hip", "(long)N * Hp * Wp > 0x7fffffffL"): [("refusal", "planes_to_u16")],
+    ("picture_ops.hip", "(long)N * Hp * Wp > 0x7fffffffL"): [("refusal", "planes_to_u8"), ("refusal", "planes_to_u16")],
     ("pu_fused.hip", "blocks > 0x7fffffffL"): [("refusal", "pu_fused")],
 }
 

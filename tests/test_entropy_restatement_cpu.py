@@ -283,7 +283,7 @@ def test_every_entry_point_refuses_what_its_guard_lists():
 OTHER_EXPORTS = {
     "ew_ops": {"pmctf_ew_f32", "pmctf_spynet_pack8_f32", "pmctf_lift_skip3_f32", "pmctf_nearest_up2_nhwc_f32",
                "pmctf_pixel_shuffle2_nhwc_f32", "pmctf_ffn3_mix_f32", "pmctf_lstm_gates_f32", "pmctf_lstm_gates_aten_f32",
-               "pmctf_planes_to_u8", "pmctf_ew_last_launch"},
+               "pmctf_ew_last_launch"},
     "decode_ops": {"pmctf_ll_ar_packed_size", "pmctf_ll_ar_pack_weights", "pmctf_ll_ar_scratch_floats",
                    "pmctf_ll_ar_decode_f32", "pmctf_ll_ar_decode_rules_f32", "pmctf_ll_ar_batch_form",
                    "pmctf_ll_ar_decode_batch_f32", "pmctf_fourstep_indexes_f32", "pmctf_mv_fourpart_indexes_f32"},

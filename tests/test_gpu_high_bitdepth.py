@@ -1,4 +1,4 @@
-"""High-bit-depth 4:2:0 sources on the GPU: the three kernels of csrc/picture_hbd.hip against tests/hbd_restatement.py
+"""High-bit-depth 4:2:0 sources on the GPU: the uint16_t ingest and output of csrc/picture_ops.hip and the error sums of csrc/picture_hbd.hip against tests/hbd_restatement.py
 (numpy), and the drivers end to end at 132x100 (padded to 256x128), GOP 4, 8 frames.
 
 Everything is exact, bit for bit and byte for byte; the one tolerance is 1e-9 dB on a PSNR against its own formula, a

@@ -5,6 +5,7 @@ command-line tools).
 Every expectation is a torch statement on CPU tensors, equal byte for byte: the harness's own statements
 (tests/quality_restatement.py: harness_pictures) for the RGB pictures, pmctf_gop.read_gop on the CPU for the model's
 inputs, and the formulas of rgb2ycbcr (pMCTF/utils/util.py:21-40) written out below for the RGB -> 4:2:0 converter."""
+import ctypes as C
 import json
 import os
 import subprocess
@@ -100,6 +101,115 @@ def test_planes_from_u8_equals_read_gop_on_the_cpu(cuda, tmp_path, h, w, psize):
     only = ops.planes_from_u8(torch.from_numpy(frame).to(cuda), h, w, psize=psize, originals=False)
     assert only[2] is None and only[3] is None
     assert torch.equal(only[0], got[0]) and torch.equal(only[1], got[1])
+
+
+GUARD = 64                                            # floats / bytes on either side of every guarded output
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _guarded(numel, np_dtype, dev, fill, offset=0):
+    """(whole buffer, the view of numel elements that starts GUARD + offset elements in)"""
+    buf = torch.from_numpy(np.full(numel + 2 * GUARD + offset, fill, dtype=np_dtype)).to(dev)
+    return buf, buf[GUARD + offset:GUARD + offset + numel]
+
+
+def _guards_untouched(buf, numel, fill, offset=0):
+    host = buf.cpu().numpy()
+    return bool((host[:GUARD + offset] == fill).all()) and bool((host[GUARD + offset + numel:] == fill).all())
+
+
+@pytest.mark.parametrize("h,w,psize", [(6, 10, 2), (10, 6, 2), (18, 34, 16), (100, 132, 128)])
+def test_ingest_equals_read_gop_at_every_source_alignment(cuda, tmp_path, h, w, psize):
+    """the 8-bit sibling of test_gpu_high_bitdepth.py::test_ingest_equals_the_restatement_at_every_source_alignment: the
+    source 0..3 bytes past a multiple of 4, with and without originals, every output between guards"""
+    import pmctf_gop
+    from pMCTF.hip import lib
+    from pMCTF.utils.yuv_reader import YUVReader
+    rng = np.random.default_rng(h * 1000 + w)
+    frame = rng.integers(0, 256, h * w * 3 // 2, dtype=np.uint8)
+    frame[0], frame[1], frame[h * w], frame[-1] = 0, 255, 255, 0
+    if (h, w) == (6, 10):
+        assert (h * w + (h // 2) * (w // 2)) % 2 == 1, "the Cr plane starts at an odd byte"
+    path = str(tmp_path / "one.yuv")
+    frame.tofile(path)
+    reader = YUVReader(path, w, h)
+    padded, orig, _ = pmctf_gop.read_gop(reader, 1, "cpu", psize)
+    reader.close()
+    want = [t.numpy() for t in (padded[0][0], padded[0][1], orig[0][0], orig[0][1])]
+    Hp, Wp = want[0].shape[-2:]
+    if (h, w, psize) == (18, 34, 16):
+        assert w % 4 == 2 and (Hp, Wp) == (32, 48), "rows of w % 4 = 2 bytes against padded rows of whole groups"
+    L = lib.hip()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    fill = -7.0
+    for off in range(4):
+        big = torch.from_numpy(np.concatenate((np.zeros(off, np.uint8), frame, np.zeros(4 - off, np.uint8)))).to(cuda)
+        assert big.data_ptr() % 4 == 0
+        src = big[off:off + frame.size]
+        assert src.data_ptr() % 4 == off
+        for with_org in (True, False):
+            bufs = [_guarded(e.size, np.float32, cuda, fill) for e in want]
+            views = [v for _, v in bufs]
+            assert all(v.data_ptr() % 16 == 0 for v in views[:2])
+            rc = L.pmctf_yuv420_u8_to_planes_f32(_ptr(src), _ptr(views[0]), _ptr(views[1]),
+                                                 _ptr(views[2]) if with_org else None,
+                                                 _ptr(views[3]) if with_org else None, Hp, Wp, h, w, stream)
+            assert rc == 0
+            for k, ((buf, v), e) in enumerate(zip(bufs, want)):
+                if k < 2 or with_org:
+                    got = v.cpu().numpy().reshape(e.shape)
+                    diff = np.argwhere(got.view(np.uint32) != e.view(np.uint32))
+                    assert diff.size == 0, (off, with_org, k, diff[0], got[tuple(diff[0])], e[tuple(diff[0])])
+                else:
+                    assert bool((v.cpu().numpy() == fill).all()), "null originals: nothing written"
+                assert _guards_untouched(buf, e.size, fill), (off, with_org, k)
+
+
+def _planes_with_specials(N, Hp, Wp, h, w):
+    """as _reconstruction of test_gpu_high_bitdepth.py at 8 bits: uniform in [-40, 300]; inside the crop NaN, +-inf, -0.0,
+    the values around 255 and exact ties k + 0.5"""
+    g = torch.Generator().manual_seed(N * 11 + Hp * 7 + Wp * 5 + h * 3 + w)
+    x = torch.rand((N, 1, Hp, Wp), generator=g) * 340.0 - 40.0
+    special = [float("nan"), float("inf"), float("-inf"), -0.0, 255.0, float(np.nextafter(np.float32(255), np.float32(1e9))),
+               256.0, 0.5, 1.5, 2.5, -0.5, 254.5, 255.5]
+    ties = [k + 0.5 for k in np.linspace(3, 252, 40).astype(np.int64)]
+    vals = torch.tensor(special + ties, dtype=torch.float32)
+    for n in range(N):
+        flat_idx = torch.randperm(h * w, generator=g)[:min(len(vals), h * w)]
+        x[n, 0, flat_idx // w, flat_idx % w] = vals[:len(flat_idx)]
+    return x
+
+
+@pytest.mark.parametrize("N,Hp,Wp,h,w", [(2, 3, 5, 3, 5), (3, 8, 8, 5, 1), (1, 4, 4, 4, 4), (2, 32, 48, 18, 34),
+                                         (1, 32, 48, 18, 35), (2, 66, 130, 65, 129)])
+def test_output_at_every_destination_alignment(cuda, N, Hp, Wp, h, w):
+    """pmctf_planes_to_u8 with out 0..3 bytes past a multiple of 4, guard bytes on both sides: NaN -> 0, then
+    rint(clip(x, 0, 255)), written out in numpy"""
+    from pMCTF.hip import lib, ops
+    x = _planes_with_specials(N, Hp, Wp, h, w)
+    crop = x[:, 0, :h, :w].numpy()
+    want = np.rint(np.clip(np.where(np.isnan(crop), np.float32(0), crop), 0, 255)).astype(np.uint8)
+    if h * w > 60:
+        assert np.isnan(crop).any() and np.isinf(crop).any() and (crop[np.isfinite(crop)] % 1.0 == 0.5).any()
+        assert np.signbit(crop[crop == 0]).any() and crop[np.isfinite(crop)].min() < 0 and crop[np.isfinite(crop)].max() > 255
+    if (N, h, w) == (2, 3, 5):
+        assert w % 4 == 1 and (N * h * w) % 4 == 2, "rows of w % 4 = 1 bytes, two tail bytes"
+    xd = x.to(cuda)
+    got = ops.planes_to_u8(xd, h, w)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (N, h, w) and got.is_cuda and got.is_contiguous()
+    diff = np.argwhere(got.cpu().numpy() != want)
+    assert diff.size == 0, f"{len(diff)} bytes differ, first at (n, y, x) {diff[0]}"
+    L = lib.hip()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for off in range(4):
+        buf, view = _guarded(N * h * w, np.uint8, cuda, 0xA5, offset=off)
+        assert view.data_ptr() % 4 == off
+        assert L.pmctf_planes_to_u8(_ptr(xd), _ptr(view), N, Hp, Wp, h, w, stream) == 0
+        assert np.array_equal(view.cpu().numpy().reshape(N, h, w), want), off
+        assert _guards_untouched(buf, N * h * w, 0xA5, offset=off), off
 
 
 def test_read_gop_device_equals_read_gop(cuda, tmp_path):

@@ -132,7 +132,7 @@ def _own_reconstruction(net, src, gops, scratch, bitdepth=8):
                 enc = pmctf_gop.encode_gop(net, padded, h, w, Q, scratch, skip_decoding=True, psize=g["psize"],
                                            me_downsample=g["me_downsample"])
                 rec = pmctf_gop.decode_gop(net, enc["frames_coded"])
-            out += pmctf_gop.frames_to_u16(rec, h, w, bitdepth) if bitdepth > 8 else pmctf_gop.frames_to_u8(rec, h, w)
+            out += pmctf_gop.frames_to_samples(rec, h, w, bitdepth)
     reader.close()
     return out
 

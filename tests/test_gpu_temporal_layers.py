@@ -73,7 +73,7 @@ def _expected(seq, folder, level, bitdepth=8):
     for coded in seq["full"][folder]:
         with torch.no_grad():
             rec = [p + [None] for p in lr.truncated_synthesis(seq["dec_net"], coded, level)]
-        out += pmctf_gop.frames_to_u16(rec, H, W, bitdepth) if bitdepth > 8 else pmctf_gop.frames_to_u8(rec, H, W)
+        out += pmctf_gop.frames_to_samples(rec, H, W, bitdepth)
     return out
 
 

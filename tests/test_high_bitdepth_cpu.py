@@ -1,6 +1,6 @@
 """High-bit-depth 4:2:0 sources, the parts that need no GPU: the 16-bit reader, read_gop's scaling and the parity anchor on
 the host, the picture_format.json sidecar, the "u16" hash level and tools/check_picture_hashes.py on 16-bit files, the
-public signatures, and the three entry points of csrc/picture_hbd.hip (declared, bound, exported, refusing bad arguments
+public signatures, and the three entry points of csrc/picture_ops.hip / picture_hbd.hip (declared, bound, exported, refusing bad arguments
 before anything is launched).  Everything is exact; the yardstick is tests/hbd_restatement.py and zlib.crc32."""
 import ctypes as C
 import importlib.util

@@ -15,7 +15,7 @@ from test_conv_census_cpu import launched_expressions
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "learned-pmctf_amd", "csrc")
 AUDITED = ("conv_mfma.hip", "basic_ops.hip", "ew_ops.hip", "conv_epilogue.h", "pu_fused.hip", "conv_split.hip", "estimate_ops.hip",
-           "decode_ops.hip", "picture_hbd.hip")
+           "decode_ops.hip", "picture_ops.hip")
 
 
 def _source(name):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times the high-bit-depth picture kernels (csrc/picture_hbd.hip) at 1920x1080 and 3840x2160, 10 bits, next to the code
-paths they stand beside, in one process, and writes profiles/high_bitdepth_io.json:
+"""Times the high-bit-depth picture kernels (csrc/picture_ops.hip at uint16_t, csrc/picture_hbd.hip) at 1920x1080 and
+3840x2160, 10 bits, next to the code paths they stand beside, in one process, and writes profiles/high_bitdepth_io.json:
 
   kernels  GPU time per launch of each of the three kernels: a batch of launches captured into one HIP graph, HIP events
            around each replay (the host's enqueue rate is not in the figure), and the algorithmic bytes per second that

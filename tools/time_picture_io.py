@@ -2,7 +2,7 @@
 """Times the picture input / output kernels (csrc/picture_ops.hip) on one 1920x1080 picture padded to 1920x1152, next to
 the code paths they replace, in one process, and writes profiles/picture_io.json:
 
-  kernels  GPU time per launch of each of the three kernels: a batch of launches captured into one HIP graph, HIP events
+  kernels  GPU time per launch of each of the four kernels: a batch of launches captured into one HIP graph, HIP events
            around each replay (the host's enqueue rate is not in the figure), and the algorithmic bytes per second that
            time means;
   ingest   bytes of one picture in host memory -> padded tensors and originals on the device, synchronised, host clock:
@@ -102,6 +102,7 @@ def main():
         "yuv420_to_rgb8 (a)": (lambda: ops.frame_to_rgb8(rec_y, rec_c, h, w), 4 * 1.5 * n + 3 * n),
         "yuv420_u8_to_planes (b)": (lambda: ops.planes_from_u8(frame_dev, h, w, psize), 1.5 * n + 4 * 1.5 * (npad + n)),
         "rgb8_to_yuv420 (c)": (lambda: ops.rgb8_to_yuv420(rgb_dev), 3 * n + 1.5 * n),
+        "planes_to_u8 (luma)": (lambda: ops.planes_to_u8(rec_y, h, w), 4 * n + n),
     }
     out = {"device": torch.cuda.get_device_name(0), "picture": [h, w], "padded": [Hp, Wp], "reps": a.reps,
            "warmup": a.warmup, "batch": a.batch, "runtime_copy_TBps": RUNTIME_COPY_TBS, "kernels": {}, "paths": {}}
