@@ -540,6 +540,55 @@ int pmctf_convert_chroma_u16(const uint16_t *src, uint16_t *dst, int h, int w, i
                              const void *chroma_x, const void *chroma_y, const int taps[2], int bitdepth, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Pixel layouts (csrc/picture_layout.hip): a picture of h x w as a decoder surface or a capture file holds it
+ * <-> the packed planar picture of the layout's chroma format (Y, then Cb, then Cr, tight, low-bit-aligned: what
+ * pmctf_convert_chroma_* and pmctf_yuv420_*_to_planes_f32 take).  Pure bit movement, exact.  "Word": a little-endian 16-bit
+ * word; a sample v of depth b is stored in a word as v << (16 - b).
+ *   NV12 / NV21 / NV16 (u8 entries, 4:2:0, 4:2:0, 4:2:2): h rows of w Y bytes, then h/2 (NV16: h) rows of w bytes
+ *     Cb0 Cr0 Cb1 Cr1 .. (NV21: Cr first).  P010 / P012 / P016 and P210 / P212 / P216 (u16 entries, bitdepth 10, 12, 16):
+ *     NV12 and NV16 in words.  The chroma plane has the luma plane's pitch and starts at pitch * luma_rows.
+ *   YUYV / UYVY (u8, 4:2:2): rows of 2w bytes Y0 Cb Y1 Cr / Cb Y0 Cr Y1 per pixel pair.  Y210 / Y212 / Y216 (u16): YUYV in
+ *     words.
+ *   V210 (u16 entries, bitdepth 10, 4:2:2): six pixels in four little-endian 32-bit words of three 10-bit values at bits
+ *     0-9, 10-19, 20-29: (Cb0, Y0, Cr0) (Y1, Cb1, Y2) (Cr1, Y3, Cb2) (Y4, Cr2, Y5); a row is ((w + 47) / 48) * 128 bytes.
+ *   pitch: bytes from one row to the next; a multiple of the container (1, 2; 4 for V210), at least the row's bytes and at
+ *   most 2^20.  luma_rows: rows of the luma plane of a semi-planar surface, h..2^17 (validated for every layout, used by
+ *   the semi-planar ones).  surface: aligned to the container; the planar picture: to its sample.
+ *   Unpacking drops the low 16 - b bits of a word and ignores bits 30-31 of a V210 word, V210 values beyond the width and
+ *   everything between a row's end and the pitch.  Packing masks every sample to b bits, writes the low 16 - b bits, V210
+ *   bits 30-31, V210 values beyond the width and the rest of a V210 row as zero, and writes nothing between a row's end
+ *   and the pitch, nor anywhere else outside the rows.  Source and destination may not overlap (not checked).
+ * One launch per picture, all planes in one grid, no LDS, no synchronisation; byte offsets are 64-bit.  PMCTF_EINVAL, before
+ * the launch, for a null pointer, a side that is odd, not positive or above 16384, an unknown layout or one of the other
+ * sample width, a bitdepth that is not the layout's, a pitch or luma_rows outside the rules, a pointer less aligned than
+ * stated. */
+#define PMCTF_LAYOUT_NV12 1
+#define PMCTF_LAYOUT_NV21 2
+#define PMCTF_LAYOUT_NV16 3
+#define PMCTF_LAYOUT_P010 4
+#define PMCTF_LAYOUT_P012 5
+#define PMCTF_LAYOUT_P016 6
+#define PMCTF_LAYOUT_P210 7
+#define PMCTF_LAYOUT_P212 8
+#define PMCTF_LAYOUT_P216 9
+#define PMCTF_LAYOUT_YUYV 10
+#define PMCTF_LAYOUT_UYVY 11
+#define PMCTF_LAYOUT_Y210 12
+#define PMCTF_LAYOUT_Y212 13
+#define PMCTF_LAYOUT_Y216 14
+#define PMCTF_LAYOUT_V210 15
+#define PMCTF_LAYOUT_MAX_PITCH (1 << 20)
+#define PMCTF_LAYOUT_MAX_LUMA_ROWS (1 << 17)
+int pmctf_unpack_layout_u8(const void *surface, uint8_t *frame, int layout, int h, int w, int64_t pitch, int luma_rows,
+                           void *stream);
+int pmctf_unpack_layout_u16(const void *surface, uint16_t *frame, int layout, int h, int w, int bitdepth, int64_t pitch,
+                            int luma_rows, void *stream);
+int pmctf_pack_layout_u8(const uint8_t *frame, void *surface, int layout, int h, int w, int64_t pitch, int luma_rows,
+                         void *stream);
+int pmctf_pack_layout_u16(const uint16_t *frame, void *surface, int layout, int h, int w, int bitdepth, int64_t pitch,
+                          int luma_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Sequence structure pre-analysis (csrc/scene_ops.hip): the luma histogram of one picture and its sum of absolute
  * differences against the previous one, the figures pmctf_seq.scene_cuts decides scene changes from.
  *

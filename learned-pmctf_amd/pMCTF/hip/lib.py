@@ -90,6 +90,10 @@ _SIGS = {
     "pmctf_resize_yuv420_u16": (ci, [vp, vp] + [ci] * 4 + [vp] * 5 + [ci, vp]),
     "pmctf_convert_chroma_u8": (ci, [vp, vp] + [ci] * 4 + [vp] * 3 + [ci, vp]),
     "pmctf_convert_chroma_u16": (ci, [vp, vp] + [ci] * 4 + [vp] * 3 + [ci, vp]),
+    "pmctf_unpack_layout_u8": (ci, [vp, vp, ci, ci, ci, i64, ci, vp]),
+    "pmctf_unpack_layout_u16": (ci, [vp, vp, ci, ci, ci, ci, i64, ci, vp]),
+    "pmctf_pack_layout_u8": (ci, [vp, vp, ci, ci, ci, i64, ci, vp]),
+    "pmctf_pack_layout_u16": (ci, [vp, vp, ci, ci, ci, ci, i64, ci, vp]),
     "pmctf_luma_activity_f32": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
     "pmctf_crc32_segments": (ci, [vp, ci, ci, vp, vp]),
     "pmctf_math_probe_f32": (ci, [ci, vp, C.c_uint32, i64, vp, cf, vp]),          # diagnostic: never on the codec's path

@@ -870,6 +870,125 @@ def convert_chroma(frame, h, w, fmt_in, fmt_out, tables, taps, bitdepth=8):
 
 
 # ------------------------------------------------------------------------------------------------
+# pixel layouts (csrc/picture_layout.hip)
+# name -> (PMCTF_LAYOUT_* code, chroma format, bitdepth, container bytes, family)
+LAYOUTS = {
+    "nv12": (1, "420", 8, 1, "semi"), "nv21": (2, "420", 8, 1, "semi"), "nv16": (3, "422", 8, 1, "semi"),
+    "p010": (4, "420", 10, 2, "semi"), "p012": (5, "420", 12, 2, "semi"), "p016": (6, "420", 16, 2, "semi"),
+    "p210": (7, "422", 10, 2, "semi"), "p212": (8, "422", 12, 2, "semi"), "p216": (9, "422", 16, 2, "semi"),
+    "yuyv": (10, "422", 8, 1, "pair"), "uyvy": (11, "422", 8, 1, "pair"),
+    "y210": (12, "422", 10, 2, "pair"), "y212": (13, "422", 12, 2, "pair"), "y216": (14, "422", 16, 2, "pair"),
+    "v210": (15, "422", 10, 4, "v210"),
+}
+LAYOUT_MAX_PITCH = 1 << 20
+LAYOUT_MAX_LUMA_ROWS = 1 << 17
+
+
+def layout_row_bytes(layout, w):
+    """bytes of one row of a picture of width w in `layout`, without pitch padding (a v210 row ends on 128 bytes)"""
+    _, _, _, container, family = LAYOUTS[layout]
+    if family == "v210":
+        return (w + 47) // 48 * 128
+    return (2 if family == "pair" else 1) * w * container
+
+
+def layout_geometry(layout, h, w, bitdepth=None, pitch=None, luma_rows=None):
+    """-> (pitch, luma_rows, frame_bytes) of an h x w picture in `layout`, the defaults filled in (pitch: the row's bytes,
+    luma_rows: h); frame_bytes is the offset of the last row's end.  ValueError naming the argument for an unknown layout,
+    a bitdepth that is not the layout's, a pitch that is no multiple of the container, below the row's bytes or above
+    2^20, luma_rows below h or above 2^17."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"pixel_layout is one of {sorted(LAYOUTS)} (got {layout!r})")
+    h, w = _picture_size(h, w)
+    _, fmt, depth, container, family = LAYOUTS[layout]
+    if bitdepth is not None and bitdepth != depth:
+        raise ValueError(f"bitdepth {bitdepth!r} contradicts pixel_layout {layout!r}, which has {depth} bits")
+    row = layout_row_bytes(layout, w)
+    if pitch is None:
+        pitch = row
+    if isinstance(pitch, bool) or not isinstance(pitch, int) or pitch % container or not row <= pitch <= LAYOUT_MAX_PITCH:
+        raise ValueError(f"pitch is a multiple of {container} bytes from {row} (a {layout} row of {w} pixels) to "
+                         f"{LAYOUT_MAX_PITCH} (got {pitch!r})")
+    if luma_rows is None:
+        luma_rows = h
+    if isinstance(luma_rows, bool) or not isinstance(luma_rows, int) or not h <= luma_rows <= LAYOUT_MAX_LUMA_ROWS:
+        raise ValueError(f"luma_rows is {h} (the height) to {LAYOUT_MAX_LUMA_ROWS} (got {luma_rows!r})")
+    if family == "semi":
+        hc = h // CHROMA_SUBSAMPLING[fmt][1]
+        return pitch, luma_rows, pitch * luma_rows + (hc - 1) * pitch + row
+    return pitch, luma_rows, (h - 1) * pitch + row
+
+
+def _layout_call(kind, planar, surface, layout, h, w, bitdepth, pitch, luma_rows):
+    code, _, depth, _, _ = LAYOUTS[layout]
+    args = (_ptr_of(surface), _ptr_of(planar)) if kind == "unpack" else (_ptr_of(planar), _ptr_of(surface))
+    if depth == 8:
+        fn = getattr(_lib.hip(), f"pmctf_{kind}_layout_u8")
+        rc = fn(*args, code, h, w, pitch, luma_rows, _stream())
+    else:
+        fn = getattr(_lib.hip(), f"pmctf_{kind}_layout_u16")
+        rc = fn(*args, code, h, w, depth, pitch, luma_rows, _stream())
+    _lib.check(rc, f"{kind}_layout({layout})")
+
+
+def _ptr_of(t):
+    assert t.is_cuda and t.is_contiguous(), "expect a dense device tensor"
+    return C.c_void_p(t.data_ptr())
+
+
+def _check_surface(surface, need, what):
+    if not isinstance(surface, torch.Tensor) or surface.dtype != torch.uint8 or surface.dim() != 1 or \
+            not surface.is_contiguous():
+        raise ValueError(f"{what}: a surface is a dense 1-D uint8 tensor")
+    if surface.numel() < need:
+        raise ValueError(f"{what}: the surface has {surface.numel()} bytes, the picture needs {need}")
+
+
+def unpack_layout(surface, layout, h, w, bitdepth=None, pitch=None, luma_rows=None, out=None):
+    """One picture as a surface or a capture file holds it (1-D uint8 device tensor of at least frame_bytes bytes, see
+    layout_geometry) -> the packed planar picture of the layout's chroma format (uint8 at 8 bits, uint16 above; Y, Cb, Cr,
+    tight, low-bit-aligned).  out: a dense tensor of that type and size to write into.  One launch."""
+    pitch, luma_rows, need = layout_geometry(layout, h, w, bitdepth, pitch, luma_rows)
+    _, fmt, depth, container, _ = LAYOUTS[layout]
+    _check_surface(surface, need, "unpack_layout")
+    dev = _dev(surface)
+    if surface.data_ptr() % container:
+        raise ValueError(f"unpack_layout: a {layout} surface is aligned to {container} bytes")
+    dtype, n = torch.uint8 if depth == 8 else torch.uint16, chroma_frame_samples(h, w, fmt)
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.numel() != n or not out.is_contiguous() or \
+            _dev(out) != dev:
+        raise ValueError(f"unpack_layout: out is a dense {dtype} tensor of {n} samples on the surface's device")
+    _layout_call("unpack", out, surface, layout, h, w, depth, pitch, luma_rows)
+    return out
+
+
+def pack_layout(frame, layout, h, w, bitdepth=None, pitch=None, luma_rows=None, out=None):
+    """The inverse of unpack_layout: a packed planar picture -> its surface (1-D uint8 device tensor of frame_bytes bytes).
+    out: a dense 1-D uint8 tensor of at least frame_bytes bytes to write into; what lies between a row's end and the pitch,
+    between the planes and after the picture is left as it is.  Without out, such bytes are zero.  One launch."""
+    pitch, luma_rows, need = layout_geometry(layout, h, w, bitdepth, pitch, luma_rows)
+    _, fmt, depth, container, _ = LAYOUTS[layout]
+    dtype, n = torch.uint8 if depth == 8 else torch.uint16, chroma_frame_samples(h, w, fmt)
+    if not isinstance(frame, torch.Tensor) or frame.dtype != dtype or frame.numel() != n:
+        raise ValueError(f"pack_layout: a {h}x{w} {layout} picture is a {dtype} tensor of {n} samples")
+    dev = _dev(frame)
+    frame = frame.contiguous()
+    if out is None:
+        tight = pitch == layout_row_bytes(layout, w) and luma_rows == h
+        out = (torch.empty if tight else torch.zeros)(need, dtype=torch.uint8, device=dev)
+    else:
+        _check_surface(out, need, "pack_layout")
+        if _dev(out) != dev:
+            raise ValueError("pack_layout: out lives on the picture's device")
+    if out.data_ptr() % container:
+        raise ValueError(f"pack_layout: a {layout} surface is aligned to {container} bytes")
+    _layout_call("pack", frame, out, layout, h, w, depth, pitch, luma_rows)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # sequence structure pre-analysis (csrc/scene_ops.hip)
 def luma_activity(cur, prev, bitdepth=8, hist=None, sad=None):
     """The luma histogram of one picture and its sum of absolute differences against the previous one, in integers at

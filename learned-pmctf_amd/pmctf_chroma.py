@@ -391,20 +391,26 @@ def read_source_format(bin_folder):
 # ------------------------------------------------------------------------------------------------------------ encoding
 class SourcePipeline:
     """The one description of a source's way into the codec that the encoders' bodies take (pmctf_gop.SequenceEncode): an
-    optional step to 4:2:0 (to420: a Converter), an optional step to the coded size (size: a pmctf_scale.CodedSize), format
-    first, size second, and the one hook that applies them (ingest).  source_size: (width, height) of the source; coded:
+    optional step out of a pixel layout (layout: a pmctf_layout.Unpacker), an optional step to 4:2:0 (to420: a
+    Converter), an optional step to the coded size (size: a pmctf_scale.CodedSize), layout first, format second, size
+    third.  The layout's step is applied by read_gop_device to the uploaded bytes of a picture (the reader carries the
+    Unpacker), the other two by the one hook ingest gives it.  chroma_format is then the layout's.  source_size: (width, height) of the source; coded:
     of what enters the codec.  y4m: the source is a .y4m file.  A .y4m or a source that is not 4:2:0 is read by
-    PlanarReader and recorded in source_format.json; a raw 4:2:0 file by YUVReader, with no record of its format.
+    PlanarReader and recorded in source_format.json; a raw 4:2:0 file by YUVReader, with no record of its format; a source
+    in a pixel layout by pmctf_layout.PackedReader, recorded as the planar source of its chroma format is.
     A raw 4:2:0 source without a coded size has no pipeline at all (None)."""
 
     def __init__(self, source_size, chroma_format="420", chroma_loc="center", to420=None, size=None, frame_rate=None,
-                 y4m=False):
+                 y4m=False, layout=None):
         self.source, self.chroma_format, self.chroma_loc = source_size, chroma_format, chroma_loc
-        self.to420, self.size, self.frame_rate = to420, size, frame_rate
+        self.to420, self.size, self.frame_rate, self.layout = to420, size, frame_rate, layout
         self.planar = y4m or chroma_format != "420"
         self.coded = source_size if size is None else size.coded
 
     def open_reader(self, src_file, width, height, bitdepth=8):
+        if self.layout is not None:
+            import pmctf_layout
+            return pmctf_layout.PackedReader(src_file, self.layout)
         if self.planar:
             return PlanarReader(src_file, width, height, 0, bitdepth, self.chroma_format, self.chroma_loc)
         from pMCTF.utils.yuv_reader import YUVReader
@@ -521,17 +527,23 @@ class OutputFormat:
         self.from420 = None if self.chroma_format == "420" else \
             Converter(self.size[0], self.size[1], "420", self.chroma_format, device, bitdepth, self.chroma_loc)
 
-    def pictures(self, frames_rec):
-        """reconstructed (padded, float) pictures -> [(Y, Cb, Cr)] integer arrays: rounded as frames_to_u8 / frames_to_u16
-        round them, resampled to the display size if there is one, then converted to the output's chroma format"""
-        (cw, ch), (W, H) = self.coded, self.size
+    def frames(self, frames_rec):
+        """reconstructed (padded, float) pictures -> the packed integer pictures on the device: rounded as frames_to_u8 /
+        frames_to_u16 round them, resampled to the display size if there is one, then converted to the output's chroma
+        format"""
+        cw, ch = self.coded
         if self.display is not None:
             frames = self.display.frames(frames_rec)
         else:
             frames = [pmctf_scale.pack_frame(rec[0], rec[1], ch, cw, self.bitdepth) for rec in frames_rec]
         if self.from420 is not None:
             frames = [self.from420(f) for f in frames]
-        return [unpack_frame(f, H, W, self.chroma_format) for f in frames]
+        return frames
+
+    def pictures(self, frames_rec):
+        """-> [(Y, Cb, Cr)] integer arrays of frames(frames_rec)"""
+        W, H = self.size
+        return [unpack_frame(f, H, W, self.chroma_format) for f in self.frames(frames_rec)]
 
     def rgb8(self, frames_rec):
         """the PNGs' pictures: those of the 4:2:0 pictures, at the display size if there is one"""

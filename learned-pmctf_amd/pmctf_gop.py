@@ -365,17 +365,23 @@ def read_gop_device(reader, gop, device, psize=128):
     (pmctf_rgb8_to_yuv420_u8).  A YUVReader of 16-bit samples goes through pmctf_yuv420_u16_to_planes_f32 the same way.
     A reader with a `resample` attribute (pmctf_chroma.SourcePipeline.ingest: a source in another chroma format, or coded at
     another size than its own) has every packed picture converted on the device before the planes are made; the triple is
-    then that of a 4:2:0 source of resample.shape."""
+    then that of a 4:2:0 source of resample.shape.  A reader with an `unpack` attribute (pmctf_layout.PackedReader and
+    SurfaceReader: pictures in a pixel layout) gives a picture's raw bytes, as an array or as a tensor that already lies
+    on the device; they are unpacked there into the packed planar picture by one launch, before anything else."""
     import numpy as np
     from pMCTF.hip import ops
     _need_gpu(device, "read_gop_device")
     padded, orig, size = [], [], None
     bitdepth = getattr(reader, "bitdepth", 8)
     resample = getattr(reader, "resample", None)
+    unpack = getattr(reader, "unpack", None)
     for _ in range(gop):
         pic = reader.read_one_frame()
         assert pic is not None, "sequence ends inside a GOP"
-        if isinstance(pic, np.ndarray):                                 # RGB picture of a PNGReader
+        if unpack is not None:                                          # the bytes of a picture in a pixel layout
+            shape = unpack.shape
+            frame = unpack((pic if isinstance(pic, torch.Tensor) else torch.from_numpy(pic)).to(device))
+        elif isinstance(pic, np.ndarray):                               # RGB picture of a PNGReader
             shape = tuple(pic.shape[:2])
             frame = ops.rgb8_to_yuv420(torch.from_numpy(pic).to(device))
         else:
@@ -1145,6 +1151,11 @@ class PlainSink:
     def pictures(self, frames_rec):
         return frames_to_samples(frames_rec, *self.shape, self.bitdepth)
 
+    def frames(self, frames_rec):
+        """the packed pictures on the device, for a sink that goes on from there (pmctf_layout.PackedSink)"""
+        import pmctf_scale
+        return [pmctf_scale.pack_frame(rec[0], rec[1], *self.shape, self.bitdepth) for rec in frames_rec]
+
     def rgb8(self, frames_rec):
         return frames_to_rgb8(frames_rec, *self.shape)
 
@@ -1195,9 +1206,10 @@ class FullDecode:
 
 
 def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=None, verify="auto", *,
-                         coded_size_output=False, coded_format_output=False):
+                         coded_size_output=False, coded_format_output=False, output_layout=None):
     """The one sequence decoder: decode_sequence_checked (mode: a FullDecode) and pmctf_layers.decode_sequence_layer (a
-    LayerDecode), and under the output flags pmctf_scale's and pmctf_chroma's forms of both.  A FullDecode and a LayerDecode
+    LayerDecode), and under the output flags pmctf_scale's and pmctf_chroma's forms of both; with an output_layout
+    (pmctf_layout) the pictures of the sink are packed on the device before they are written.  A FullDecode and a LayerDecode
     of level 0 without motion_fill decode the same pictures in the same order, so they write the same bytes."""
     import contextlib
     import time
@@ -1219,6 +1231,9 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
     mode.open(bin_folder, header, gops, verify)
     h, w = header["height"], header["width"]
     sink = picture_sink(bin_folder, yuv_out, w, h, dev, bitdepth, coded_size_output, coded_format_output)
+    if output_layout is not None:
+        import pmctf_layout
+        sink = pmctf_layout.PackedSink(sink, output_layout, yuv_out, bitdepth)
     q_indexes = gop_q_indexes(header, len(gops))
     shapes, seconds, mismatches, times = [], [], [], []
     verified = nbytes = 0

@@ -24,7 +24,9 @@ is resampled there on the GPU after the hashes, which describe the coded-size pi
 A folder coded from a .y4m or from a 4:2:2 / 4:4:4 source (it holds source_format.json) is written in the chroma format of
 its source, converted on the GPU after the resampling (pmctf_chroma); --coded-format-output writes the coded
 4:2:0 pictures instead.  An OUT path ending in .y4m becomes a Y4M file (its F tag is the recorded frame rate, 25:1 when
-there is none)."""
+there is none).
+--output-layout NAME (pmctf_layout) writes every picture in that pixel layout (nv12, p010, v210, ...), packed
+on the GPU after the steps above; the layout must have the chroma format and depth of the pictures being written."""
 import argparse
 import json
 import os
@@ -34,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "learned-pmctf_amd"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     w = ap.add_mutually_exclusive_group(required=True)
     w.add_argument("--checkpoint", help="weights file (torch.save of a state_dict, or of a dict holding one)")
@@ -55,9 +57,10 @@ def main():
                     help="a folder coded with --coded-size: write the coded-size pictures, not the display-size ones")
     ap.add_argument("--coded-format-output", action="store_true",
                     help="a folder with a source_format.json: write the coded 4:2:0 pictures, not the source's chroma format")
+    ap.add_argument("--output-layout", metavar="NAME", help="write the pictures in this pixel layout (pmctf_layout.LAYOUTS)")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     layered = a.temporal_level is not None or a.motion_fill
     if layered and (a.temporal_level or 0) < 0:
         ap.error("--temporal-level is 0 or more")
@@ -65,9 +68,16 @@ def main():
         ap.error("--motion-fill output has no hashes: it cannot be combined with --verify")
     if a.yuv_out is None and a.png is None:
         ap.error("give OUT.yuv, --png DIR or both")
+    import pmctf_layout
+    if a.output_layout is not None:
+        try:
+            pmctf_layout.check_layout(a.output_layout, "--output-layout")
+        except ValueError as e:
+            ap.error(str(e))
+        if a.yuv_out is None or pmctf_layout.pmctf_chroma.is_y4m(a.yuv_out):
+            ap.error("--output-layout: needs an OUT file that is no .y4m (Y4M pictures are planar)")
     import torch
     import pmctf_gop
-    import pmctf_chroma
     from pMCTF.models.video.pMCTF_L import pMCTF
     header, _ = pmctf_gop.sequence_layout(a.bin_folder)
     net = pMCTF(num_me_stages=header["num_me_stages"]).eval()
@@ -82,16 +92,22 @@ def main():
     with torch.no_grad():
         try:
             if layered:
-                out = pmctf_chroma.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
+                out = pmctf_layout.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
                                                          png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
                                                          coded_size_output=a.coded_size_output,
-                                                         coded_format_output=a.coded_format_output)
+                                                         coded_format_output=a.coded_format_output,
+                                                         output_layout=a.output_layout)
             else:
-                out = pmctf_chroma.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
+                out = pmctf_layout.decode_sequence_checked(net, a.bin_folder, a.yuv_out, a.device, png_out=a.png,
                                                            verify=a.verify, coded_size_output=a.coded_size_output,
-                                                           coded_format_output=a.coded_format_output)
+                                                           coded_format_output=a.coded_format_output,
+                                                           output_layout=a.output_layout)
         except pmctf_gop.PictureHashMismatch as e:
             sys.exit(f"picture hash mismatch: {e}")
+        except ValueError as e:
+            if a.output_layout is None:
+                raise
+            sys.exit(f"--output-layout: {e}")
     n = len(out["frames"])
     height, width = out["frames"][0] if n else (header["height"], header["width"])
     print(json.dumps({"frames": n, "height": height, "width": width, "yuv": a.yuv_out, "png": a.png,

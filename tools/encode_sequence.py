@@ -32,7 +32,10 @@ tools/decode_sequence.py resamples the decoded pictures; the mean PSNR of those 
 SOURCE.y4m (pmctf_chroma): --width, --height, --bitdepth and --fps default from its header, and a 4:2:2 or
 4:4:4 file is converted to 4:2:0 on the GPU by the same filter before it is coded; --chroma-format 420|422|444 says the
 same of a raw planar file.  --chroma-loc then also tells the siting of the source (default: the header's; left for 4:2:2).
-BIN_FOLDER/source_format.json keeps the source's format and frame rate, to which tools/decode_sequence.py converts back."""
+BIN_FOLDER/source_format.json keeps the source's format and frame rate, to which tools/decode_sequence.py converts back.
+--pixel-layout NAME [--pitch BYTES] [--luma-rows N] (pmctf_layout): SOURCE is a raw file of pictures in that
+layout (nv12, nv21, nv16, p010..p216, yuyv, uyvy, y210..y216, v210), unpacked on the GPU before anything else; the layout
+says the bit depth and the chroma format, and BIN_FOLDER is the one the planar file of the same pictures codes to."""
 import argparse
 import os
 import sys
@@ -87,12 +90,36 @@ def main(argv=None):
     ap.add_argument("--coded-size", metavar="WxH", help="code at this size instead of the source's (even, within a factor of 4)")
     ap.add_argument("--chroma-loc", choices=("center", "left"),
                     help="--coded-size: where the source's chroma samples lie (center: the default; left: MPEG-2 siting)")
+    ap.add_argument("--pixel-layout", metavar="NAME", help="SOURCE holds pictures in this layout (pmctf_layout.LAYOUTS)")
+    ap.add_argument("--pitch", type=int, metavar="BYTES", help="--pixel-layout: bytes from one row to the next (default: tight)")
+    ap.add_argument("--luma-rows", type=int, metavar="N",
+                    help="--pixel-layout, semi-planar: rows of the luma plane (default: the height)")
     ap.add_argument("source", help=".yuv or .y4m file, or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args(argv)
     import pmctf_chroma
+    import pmctf_layout
     import pmctf_scale
     y4m = pmctf_chroma.is_y4m(a.source) and not os.path.isdir(a.source)
+    unpack = None
+    if a.pixel_layout is None:
+        for opt in ("pitch", "luma_rows"):
+            if getattr(a, opt) is not None:
+                ap.error(f"--{opt.replace('_', '-')}: only with --pixel-layout")
+    else:
+        if y4m or os.path.isdir(a.source):
+            ap.error("--pixel-layout: for a raw file; a .y4m is planar and PNGs are RGB")
+        if a.width is None or a.height is None:
+            ap.error("--width and --height are required with --pixel-layout")
+        try:
+            info = pmctf_layout.check_layout(a.pixel_layout, "--pixel-layout")
+            unpack = pmctf_layout.Unpacker(a.pixel_layout, a.width, a.height, a.pitch, a.luma_rows)
+        except ValueError as e:
+            ap.error(f"--pixel-layout: {e}")
+        for opt, key in (("bitdepth", "bitdepth"), ("chroma_format", "chroma_format")):
+            if getattr(a, opt) not in (None, info[key]):
+                ap.error(f"--{opt.replace('_', '-')} {getattr(a, opt)}: --pixel-layout {a.pixel_layout} has {info[key]}")
+        a.bitdepth, a.chroma_format = info["bitdepth"], info["chroma_format"]
     if y4m:
         try:
             head = pmctf_chroma.read_y4m_header(a.source)
@@ -170,7 +197,11 @@ def main(argv=None):
         if a.width is None or a.height is None:
             ap.error("--width and --height are required for a .yuv source")
         src_format, width, height = "yuv", a.width, a.height
-        if converted:
+        if unpack is not None:
+            available, rest = divmod(os.path.getsize(a.source), unpack.frame_bytes)
+            if rest:
+                ap.error(f"{a.source}: not a whole number of {a.pixel_layout} pictures of {unpack.frame_bytes} bytes")
+        elif converted:
             try:
                 available = len(pmctf_chroma.PlanarReader(a.source, width, height, 0, a.bitdepth, a.chroma_format))
             except ValueError as e:
@@ -203,23 +234,24 @@ def main(argv=None):
     os.makedirs(a.bin_folder, exist_ok=True)
     common = dict(src_format=src_format, decoded_frame_path=a.decoded_frames, msssim=a.msssim, picture_hash=a.picture_hash,
                   bitdepth=a.bitdepth, coded_size=coded_size, chroma_loc=a.chroma_loc, chroma_format=a.chroma_format)
+    common.update(pixel_layout=a.pixel_layout, pitch=a.pitch, luma_rows=a.luma_rows)
     with torch.no_grad():
         if fixed:
-            out = pmctf_chroma.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+            out = pmctf_layout.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
                                              keep_gops=True, **common)
         else:
             import pmctf_seq
             cuts = dict(structure=a.structure, hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
                         mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min)
             if rate is not None:
-                out = pmctf_chroma.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
+                out = pmctf_layout.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
                                                        a.bin_folder, a.device, **cuts, **common, **rate)
                 for k, r in enumerate(out["rate"]):
                     print(f"GOP {k}: q_index {r['q_index']}, {r['bits']} bits of {r['budget']}"
                           f"{'' if r['fits'] else ' (does not fit)'}, {len(r['trials'])} trial(s), credit {r['credit']}",
                           file=sys.stderr)
             else:
-                out = pmctf_chroma.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                out = pmctf_layout.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
                                                         a.device, **cuts, **common)
             if "cuts" in out:
                 print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
