@@ -331,6 +331,17 @@ class HipEngine:
             pair_plan.RESOURCES.adopt(self, dict(ctx))       # the streams outlive the engine until the next safe point
         return ctx
 
+    def owned_streams(self):
+        """Read-only: name -> every stream this engine has created so far (the calling host thread's plan streams once
+        plan_context() made them).  For tests that put a delay on one of them (tests/stream_order.py)."""
+        out = {f"side{i}": s for i, s in enumerate(self.side_streams)}
+        out["motion"] = self.motion_stream
+        out.update({f"batch{i}": s for i, s in enumerate(self.batch_streams)})
+        ctx = self._plan_ctx.get(threading.get_ident())
+        if ctx is not None:
+            out.update({"plan_luma": ctx["streams"][0], "plan_chroma": ctx["streams"][1], "plan_capture": ctx["capture"]})
+        return out
+
     def release(self):
         """drop the captured launch plans (their graphs hold device memory pools) — called when the model replaces the
         engine or goes away.  May run at ANY moment (a finaliser): it only lets go of the plans; their device objects
