@@ -290,10 +290,9 @@ class HipEngine:
         # encode_one_stage replays captured launch plans (HIP graphs, pMCTF.hip.pair_plan) from the second pair of a
         # configuration on: luma and chroma coders on two streams, no per-launch host work
         self.use_graphs = os.environ.get("PMCTF_GRAPHS", "1") != "0"
-        self._dec_pool = None
-        self._batch_pool = None
+        self._batch_pool = None         # (workers, executor) of the host threads that finish files (_finish_files)
         self.batch_streams = []         # one per geometry group of a batched decode (pwave_decompress_batch_begin)
-        # host threads that finish the files of a batched decode (at most 16).  Measured on a 1080p GOP 16 (32 files,
+        # host threads that finish the files of a pair's or a batched decode (at most 16).  Measured on a 1080p GOP 16 (32 files,
         # tools/time_decode_gop.py): 2.93 / 2.89 / 2.98 / 3.03 s with 2 / 4 / 8 / 16 threads — the threads spend their time
         # in Python between launches and host range decoding, so more of them only contend
         self.decode_workers = 4
@@ -684,7 +683,18 @@ class HipEngine:
             stream = SymbolStream(hz * wz * cz + 4 * 16 * hy * wy, self.dev)
             z_hat = ops.z_symbols(mv_z, stream.sym, stream.idx, stream.take(hz * wz * cz, f"z{s}"))
         common = self.mv_prior_param_decoder(z_hat, self.to_nhwc_input(dpb["ref_mv_y"]), s)
-        so_far = torch.empty_like(mv_y)
+        out = self.mv_fourpart(s, common, bits_y if estimate else stream, q_dec, me_downsample, mv_y)
+        out.update({"stream": stream, "est_mv": est_mv, "mv_y": mv_y, "z_hat": z_hat, "common": common})
+        if estimate:
+            out["bits_y"], out["bits_z"] = bits_y.bits, bits_z.bits
+        return out
+
+    def mv_fourpart(self, s, common, io, q_dec, me_downsample, mv_y=None):
+        """The four-part spatial prior of the motion latent and what follows it (pMCTF_L.py:244-292, 448-495, 497-523):
+        the ONE body the encoder, the estimator and the decoder evaluate.  io: SymbolStream, BitSink or HostDecoder
+        (_mv_fourpart); mv_y: the latent to code (none when decoding)."""
+        _, hy, wy, _ = common.shape
+        so_far = torch.empty((1, hy, wy, 64), dtype=torch.float32, device=self.dev)
         sp = None
         for t in range(4):
             if t > 0:
@@ -692,20 +702,24 @@ class HipEngine:
                 for i in range(3):
                     x = self.depth_conv_block(f"mv_y_spatial_prior.{s}.{i}", x)
                 sp = x
-            if estimate:
-                ops.mv_fourpart_estimate(mv_y, common, sp, so_far, t, bits_y.bits)
-            else:
-                ops.mv_fourpart_step(mv_y, common, sp, so_far, stream.sym, stream.idx,
-                                     stream.take(16 * hy * wy, "gauss"), t, self.lmin, self.lstep)
+            self._mv_fourpart(io, mv_y, common, sp, so_far, t)
         mv_y_hat = ops.mv_dequant(so_far, common)
         mv_hat, mv_feature = self.mv_dec(s, mv_y_hat, q_dec)
-        if me_downsample > 1:       # pMCTF_L.py:274-275,475-476
+        if me_downsample > 1:       # pMCTF_L.py:274-275,475-476,516-517
             mv_hat = ops.bilinear_up2(mv_hat, float(me_downsample), me_downsample)
-        out = {"stream": stream, "mv_hat": mv_hat, "mv_feature": mv_feature, "mv_y_hat": mv_y_hat,
-               "est_mv": est_mv, "mv_y": mv_y, "z_hat": z_hat, "common": common}
-        if estimate:
-            out["bits_y"], out["bits_z"] = bits_y.bits, bits_z.bits
-        return out
+        return {"mv_hat": mv_hat, "mv_feature": mv_feature, "mv_y_hat": mv_y_hat}
+
+    def _mv_fourpart(self, io, mv_y, common, sp, so_far, t):
+        """the element step of part t: bit estimates, symbols out, or symbols in"""
+        _, hy, wy, _ = so_far.shape
+        if isinstance(io, BitSink):
+            ops.mv_fourpart_estimate(mv_y, common, sp, so_far, t, io.bits)
+        elif isinstance(io, HostDecoder):
+            idx = ops.mv_fourpart_indexes(common, sp, hy, wy, t, self.lmin, self.lstep)
+            ops.mv_fourpart_dequant(self._decode(io, idx, "gauss"), common, sp, so_far, t)
+        else:
+            ops.mv_fourpart_step(mv_y, common, sp, so_far, io.sym, io.idx, io.take(16 * hy * wy, "gauss"), t, self.lmin,
+                                 self.lstep)
 
     # ------------------------------------------------------------------ a10 learned lifting DWT
     def lift_branch(self, wt, conv_name, pu_name, x, skip_rule):
@@ -793,10 +807,11 @@ class HipEngine:
         o = self.conv(p + ".conv1", 1, 1)(x, act=ACT_LEAKY, slope=0.2)
         return self.conv(p + ".conv2", 1, 1)(o, res1=x, res2=res2)
 
-    def fusion_compress(self, p, x, ctx, prev, stream):
-        """ContextFusionFourStep.forward(write=True) (context_fusion_4step.py:139-191).
-        x: plane (N,1,h,w); ctx: NHWC (N,h,w,1); prev: plane of the previous level's subband or None."""
-        N, _, H, W = x.shape
+    def fusion(self, p, ctx, prev, io, N, H, W, x=None):
+        """ContextFusionFourStep.forward(write=True) and .decompress (context_fusion_4step.py:139-191, 196-249): the ONE
+        body the encoder, the estimator and the decoder evaluate for a subband of (N, H, W).
+        ctx: NHWC (N,H,W,1); prev: plane of the previous level's subband or None; io: SymbolStream, BitSink or
+        HostDecoder (_fourstep); x: the plane (N,1,H,W) to code (none when decoding).  Returns the quantised plane."""
         if prev is not None:
             up = ops.nearest_up2(prev.view(N, H // 2, W // 2, 1))
             prevc = self.conv(p + ".lower_level_subband.1", 1, 1)(up)
@@ -805,9 +820,8 @@ class HipEngine:
         c = self.context_residual(p + ".y_hierarchical_prior_enc.0", c)
         c = self.context_residual(p + ".y_hierarchical_prior_enc.1", c)
         params = self.depth_conv_block(p + ".y_hierarchical_prior_out", c)
-        so_far = torch.empty_like(x)
-        n = N * H * W
-        self._fourstep(stream, x, params, so_far, 0, n)
+        so_far = torch.empty((N, 1, H, W), dtype=torch.float32, device=self.dev)
+        self._fourstep(io, x, params, so_far, 0)
         for step in (1, 2, 3):
             t = self.conv(f"{p}.y_spatial_prior_{step}.0", 1, 1)(so_far.view(N, H, W, 1))
             t = self.context_residual(f"{p}.y_spatial_prior_{step}.1", t, res2=c)      # (.. + x) + context
@@ -825,14 +839,20 @@ class HipEngine:
             else:
                 t = self.context_residual(f"{p}.y_spatial_prior_{step}_out.1", t)
                 params = self.conv(f"{p}.y_spatial_prior_{step}_out.2")(t)
-            self._fourstep(stream, x, params, so_far, step, n)
+            self._fourstep(io, x, params, so_far, step)
         return so_far
 
-    def _fourstep(self, sink, x, params, so_far, step, n):
-        if isinstance(sink, BitSink):
-            ops.fourstep_estimate(x, params, so_far, step, sink.bits)
+    def _fourstep(self, io, x, params, so_far, step):
+        """the element step behind each `params`: bit estimates, symbols out, or symbols in"""
+        N, _, H, W = so_far.shape
+        if isinstance(io, BitSink):
+            ops.fourstep_estimate(x, params, so_far, step, io.bits)
+        elif isinstance(io, HostDecoder):
+            idx = ops.fourstep_indexes(params, N, H, W, step, self.lmin, self.lstep)
+            ops.fourstep_dequant(self._decode(io, idx, "gauss"), params, so_far, step)
         else:
-            ops.fourstep_quant(x, params, so_far, sink.sym, sink.idx, sink.take(n, "gauss"), step, self.lmin, self.lstep)
+            ops.fourstep_quant(x, params, so_far, io.sym, io.idx, io.take(N * H * W, "gauss"), step, self.lmin,
+                               self.lstep)
 
     # ------------------------------------------------------------------ a13 conv-LSTM context (long_context.py)
     def lstm(self, p, x, state):
@@ -929,7 +949,6 @@ class HipEngine:
             ll = y[lvl]["ll"]
         stream = BitSink(N, self.dev) if estimate else SymbolStream(self.pwave_symbol_count(N, H, W), self.dev,
                                                                     merge=not per_push)
-        hat = {lvl: {} for lvl in range(self.L)}
         llq = ew(EW_ROUND_CLAMP_MULS, ll, alpha=q_scale_ll, beta=clip)
         params = self.context_fusion_ll(coder, llq)
         if estimate:        # pWave.py:255-263: the rounded LL itself is kept; bits of the unrounded residual
@@ -938,8 +957,27 @@ class HipEngine:
         else:
             ll_hat = ops.ll_quant(llq, params, stream.sym, stream.idx, stream.take(llq.numel(), "gauss"), self.lmin,
                                   self.lstep, ar_order)
+        hat = self.pwave_walk(coder, ll_hat, stream,
+                              lambda lvl, sb: ew(EW_CLAMP_MULS, y[lvl][sb], alpha=q_scale, beta=clip))
+        # the synthesis is needed for the reconstruction only, not for the bitstream, so a caller may run it after the
+        # stream has been handed to the range coder
+        synthesis = lambda: self.pwave_synthesis(coder, hat, q_scale, q_scale_ll)
+        if defer:
+            return synthesis, stream
+        x_hat = synthesis()
+        if estimate:
+            return x_hat, stream, hat
+        return x_hat, stream
+
+    def pwave_walk(self, coder, ll_hat, io, coded=lambda lvl, sb: None):
+        """The subbands below the LL subband, levels L-1..0 and lh, hl, hh in coding order (pWave.py:381-463, 467-529):
+        the ONE walk the encoder, the estimator and the decoder make.  ll_hat: the quantised LL plane (N,1,h,w), which
+        fixes the geometry of every level; io: SymbolStream, BitSink or HostDecoder; coded(lvl, sb): the plane to code
+        (an encoder's; launched between the context slice and the fusion).  Returns hat[lvl][sb]."""
+        N = ll_hat.shape[0]
+        hat = {lvl: {} for lvl in range(self.L)}
         hat[self.L - 1]["ll"] = ll_hat
-        lstm_state = self.ctx_init(N, ll.shape[2], ll.shape[3])
+        lstm_state = self.ctx_init(N, ll_hat.shape[2], ll_hat.shape[3])
         context = self.ctx_forward_one_subband(coder, lstm_state, ll_hat, "ll", self.L - 1)
         for lvl in range(self.L - 1, -1, -1):
             for sidx, sb in enumerate(("lh", "hl", "hh")):
@@ -947,29 +985,22 @@ class HipEngine:
                 ctx = ops.empty_nhwc(N, h, w, 1, self.dev)
                 ew(EW_COPY, as_nchw(context)[:, sidx:sidx + 1], out=as_nchw(ctx))
                 prev = hat[lvl + 1][sb] if lvl < self.L - 1 else None
-                s_curr = ew(EW_CLAMP_MULS, y[lvl][sb], alpha=q_scale, beta=clip)
-                s_hat = self.fusion_compress(f"{coder}.context_fusion.{lvl}.{sb}", s_curr, ctx, prev, stream)
+                s_hat = self.fusion(f"{coder}.context_fusion.{lvl}.{sb}", ctx, prev, io, N, h, w, coded(lvl, sb))
                 hat[lvl][sb] = s_hat
                 context = self.ctx_forward_one_subband(coder, lstm_state, s_hat, sb, lvl)
-        def synthesis():
-            """dequantise, inverse DWT, post-process (pWave.py:446-455): needed for the reconstruction only, not for
-            the bitstream, so a caller may run it after the stream has been handed to the range coder"""
-            out = None
-            rec_ll = ew(EW_DIVS, hat[self.L - 1]["ll"], alpha=q_scale_ll)
-            for lvl in range(self.L - 1, -1, -1):
-                sbs = {"ll": rec_ll}
-                for sb in ("lh", "hl", "hh"):
-                    sbs[sb] = ew(EW_DIVS, hat[lvl][sb], alpha=q_scale)
-                out = self.backward_lift_2d(coder, sbs)
-                rec_ll = out
-            return self.post_process(coder, out, 256.0, 256.0)
+        return hat
 
-        if defer:
-            return synthesis, stream
-        x_hat = synthesis()
-        if estimate:
-            return x_hat, stream, hat
-        return x_hat, stream
+    def pwave_synthesis(self, coder, hat, q_scale, q_scale_ll):
+        """dequantise, inverse DWT, post-process (pWave.py:446-455; the tail of pWave.decompress)"""
+        out = None
+        rec_ll = ew(EW_DIVS, hat[self.L - 1]["ll"], alpha=q_scale_ll)
+        for lvl in range(self.L - 1, -1, -1):
+            sbs = {"ll": rec_ll}
+            for sb in ("lh", "hl", "hh"):
+                sbs[sb] = ew(EW_DIVS, hat[lvl][sb], alpha=q_scale)
+            out = self.backward_lift_2d(coder, sbs)
+            rec_ll = out
+        return self.post_process(coder, out, 256.0, 256.0)
 
     # ------------------------------------------------------------------ estimate-mode stage (pMCTF_L.py:332-379)
     def forward_one_stage(self, ref, cur, q_index, code_lt, dpb, mv_hat=None, stage_idx=0, me_downsample=1):
@@ -1129,29 +1160,42 @@ class HipEngine:
             rules.append(r(N, H, W) if callable(r) else r)
         return rules
 
-    def ll_ar_launch(self, coder, dec, N, H, W, stream=None):
-        """Enqueue the sequential LL decode (one persistent workgroup) on `stream`; returns a ticket for ll_ar_finish.
-        The LL streams of different files are independent, so callers start all of them before waiting for any."""
-        if N > 4:
-            raise NotImplementedError("the sequential LL decoder handles up to 4 planes per stream (Y / UV / RGB)")
-        L = _lib.hip()
-        w = self._ll_weights(coder)
-        cdf, sizes, offsets = self._dev_tables("gauss")
-        x, pos = dec.get_state()
-        st = stream if stream is not None else torch.cuda.current_stream(self.dev)
+    def _ll_ar_ticket(self, dec, N, H, W, st):
+        """what one stream's sequential LL decode lives in: its words on the device, the planes, the coder state read back"""
         with torch.cuda.stream(st):
             words = torch.from_numpy(dec.words.copy()).to(self.dev)
             ll = torch.zeros((N, 1, H, W), dtype=torch.float32, device=self.dev)
-            scratch = torch.zeros(L.pmctf_ll_ar_scratch_floats(N, H, W), dtype=torch.float32, device=self.dev)
             state = torch.zeros(3, dtype=torch.int64, device=self.dev)
-            vp = lambda t: C.c_void_p(t.data_ptr())
-            rules = self._ll_rules(coder, N, H, W)
+        return {"dec": dec, "ll": ll, "state": state, "stream": st, "keep": [words]}
+
+    def _ll_ar_issue(self, coder, t, ll, n):
+        """One single-stream LL decode (one persistent workgroup) of the `n` planes `ll`, a slice of ticket t's planes,
+        from where t's host decoder stands, on t's stream.  The rules are those of all of t's planes."""
+        L = _lib.hip()
+        w = self._ll_weights(coder)
+        cdf, sizes, offsets = self._dev_tables("gauss")
+        x, pos = t["dec"].get_state()
+        N, _, H, W = t["ll"].shape
+        rules = self._ll_rules(coder, N, H, W)
+        st, words = t["stream"], t["keep"][0]
+        vp = lambda a: C.c_void_p(a.data_ptr())
+        with torch.cuda.stream(st):
+            scratch = torch.zeros(L.pmctf_ll_ar_scratch_floats(n, H, W), dtype=torch.float32, device=self.dev)
+            t["keep"].append(scratch)
             _lib.check(L.pmctf_ll_ar_decode_rules_f32(vp(w), vp(words), words.numel(), C.c_uint64(x), pos, vp(cdf),
                                                       vp(sizes), vp(offsets), cdf.shape[1], float(self.lmin),
-                                                      float(self.lstep), vp(ll), vp(scratch), N, H, W, vp(state),
+                                                      float(self.lstep), vp(ll), vp(scratch), n, H, W, vp(t["state"]),
                                                       rules[0], rules[1], rules[2], C.c_void_p(st.cuda_stream)),
                        "ll_ar_decode")
-        return {"dec": dec, "ll": ll, "state": state, "stream": st, "keep": (words, scratch)}
+
+    def ll_ar_launch(self, coder, dec, N, H, W, stream=None):
+        """Enqueue the sequential LL decode on `stream`; returns a ticket for ll_ar_finish.
+        The LL streams of different files are independent, so callers start all of them before waiting for any."""
+        if N > 4:
+            raise NotImplementedError("the sequential LL decoder handles up to 4 planes per stream (Y / UV / RGB)")
+        t = self._ll_ar_ticket(dec, N, H, W, stream if stream is not None else torch.cuda.current_stream(self.dev))
+        self._ll_ar_issue(coder, t, t["ll"], N)
+        return t
 
     def ll_ar_finish(self, t):
         t["stream"].synchronize()
@@ -1165,51 +1209,27 @@ class HipEngine:
     def ll_ar_decode(self, coder, dec, N, H, W):
         return self.ll_ar_finish(self.ll_ar_launch(coder, dec, N, H, W))
 
-    def fusion_decompress(self, p, ctx, prev, dec, N, H, W):
-        """ContextFusionFourStep.decompress (context_fusion_4step.py:196-249)"""
-        if prev is not None:
-            up = ops.nearest_up2(prev.view(N, H // 2, W // 2, 1))
-            prevc = self.conv(p + ".lower_level_subband.1", 1, 1)(up)
-            ctx = self.cat_channels(ctx, prevc)
-        c = self.conv(p + ".conv1_context", 1, 1)(ctx)
-        c = self.context_residual(p + ".y_hierarchical_prior_enc.0", c)
-        c = self.context_residual(p + ".y_hierarchical_prior_enc.1", c)
-        params = self.depth_conv_block(p + ".y_hierarchical_prior_out", c)
-        so_far = torch.empty((N, 1, H, W), dtype=torch.float32, device=self.dev)
-        for step in range(4):
-            if step > 0:
-                t = self.conv(f"{p}.y_spatial_prior_{step}.0", 1, 1)(so_far.view(N, H, W, 1))
-                t = self.context_residual(f"{p}.y_spatial_prior_{step}.1", t, res2=c)
-                t = self.context_residual(f"{p}.y_spatial_prior_{step}_out.0", t)
-                if H % 2 == 0 and W % 2 == 0:
-                    q = f"{p}.y_spatial_prior_{step}_out.1"
-                    o = self.conv(q + ".conv1", 1, 1)(t, act=ACT_LEAKY, slope=0.2)
-                    py, px = step >> 1, step & 1
-                    tq = ops.empty_nhwc(N, H // 2, W // 2, t.shape[3], self.dev)
-                    ew(EW_COPY, as_nchw(t)[:, :, py::2, px::2], out=as_nchw(tq))
-                    tq = ops.conv_at_class(self.conv(q + ".conv2", 1, 1), o, step, res1=tq)
-                    params = self.conv(f"{p}.y_spatial_prior_{step}_out.2")(tq, rule_hw=(H, W))
-                else:
-                    t = self.context_residual(f"{p}.y_spatial_prior_{step}_out.1", t)
-                    params = self.conv(f"{p}.y_spatial_prior_{step}_out.2")(t)
-            idx = ops.fourstep_indexes(params, N, H, W, step, self.lmin, self.lstep)
-            sym = self._decode(dec, idx, "gauss")
-            ops.fourstep_dequant(sym, params, so_far, step)
-        return so_far
-
-    def pwave_decompress_begin(self, coder, data, padding, q_index, qp_scale=None, stream=None):
-        """Parse one bitstream file and start its sequential LL decode; finish with pwave_decompress_end."""
+    def _open_file(self, coder, data, padding, q_index, qp_scale=None):
+        """One bitstream file -> its `begun` record, the LL decode not yet started (ticket None).  A file that is too
+        short for its header or its payload, or whose header is implausible, raises ValueError."""
         import struct
-        q_scale, q_scale_ll = self.q_scales(coder, q_index, qp_scale)
+        if len(data) < 16:
+            raise ValueError("bitstream file shorter than its header")
         height, width, N = struct.unpack(">III", data[:12])
         (n,) = struct.unpack(">I", data[12:16])
+        if not (1 <= N <= 4 and height >= 1 and width >= 1 and n >= 1 and len(data) >= 16 + n):
+            raise ValueError("bitstream file with an implausible or truncated header")
         dec = HostDecoder(self.tables, data[16:16 + n])
         new_h = (height + padding - 1) // padding * padding
         new_w = (width + padding - 1) // padding * padding
-        sh, sw = new_h >> self.L, new_w >> self.L
-        ticket = self.ll_ar_launch(coder, dec, N, sh, sw, stream)
-        return {"coder": coder, "dec": dec, "ticket": ticket, "q": (q_scale, q_scale_ll), "N": N,
-                "shape": (new_h, new_w, sh, sw)}
+        return {"coder": coder, "dec": dec, "ticket": None, "q": self.q_scales(coder, q_index, qp_scale), "N": N,
+                "shape": (new_h, new_w, new_h >> self.L, new_w >> self.L)}
+
+    def pwave_decompress_begin(self, coder, data, padding, q_index, qp_scale=None, stream=None):
+        """Parse one bitstream file and start its sequential LL decode; finish with pwave_decompress_end."""
+        b = self._open_file(coder, data, padding, q_index, qp_scale)
+        b["ticket"] = self.ll_ar_launch(coder, b["dec"], b["N"], b["shape"][2], b["shape"][3], stream)
+        return b
 
     def pwave_decompress(self, coder, data, padding, q_index, qp_scale=None):
         """pWave.decompress (pWave.py:467-529) from the bytes of one bitstream file -> x_hat plane (N,1,Hp,Wp)"""
@@ -1227,12 +1247,16 @@ class HipEngine:
         return [self.pwave_decompress_begin(*j, stream=self.side_streams[i]) for i, j in enumerate(jobs)]
 
     def pwave_decompress_many_end(self, begun):
-        if len(begun) == 1:
+        if len(begun) == 1:         # one file: on the caller's stream, no thread
             return [self.pwave_decompress_end(begun[0])]
-        # The files are independent: each is finished by its own host thread on its own stream (the four-step decode
-        # alternates GPU network evaluations with host range decoding, so one file alone leaves both sides idle half the
-        # time; ctypes and the device waits release the GIL).  Chroma's subbands are decoded while luma's four times
-        # longer sequential LL part is still running on its CU.
+        return self._finish_files(begun)
+
+    def _finish_files(self, begun, names=None):
+        """The four-step parts of the begun files.  The files are independent: each is finished by its own host thread
+        (self.decode_workers of them) on its own side stream — the four-step decode alternates GPU network evaluations
+        with host range decoding, so one file alone leaves both sides idle half the time; ctypes and the device waits
+        release the GIL.  Chroma's subbands are decoded while luma's four times longer sequential LL part is still
+        running on its CU.  names: one label per file, put in front of the ValueError a damaged file raises."""
         main = torch.cuda.current_stream(self.dev)
         ready = torch.cuda.Event()
         ready.record(main)
@@ -1241,11 +1265,28 @@ class HipEngine:
             torch.cuda.set_device(self.dev)
             st = self.side_streams[i]
             st.wait_event(ready)
-            with torch.no_grad(), torch.cuda.stream(st):
-                return self.pwave_decompress_end(begun[i])
-        if self._dec_pool is None:
-            self._dec_pool = ThreadPoolExecutor(max_workers=4)
-        out = list(self._dec_pool.map(finish, range(len(begun))))
+            try:
+                with torch.no_grad(), torch.cuda.stream(st):
+                    return self.pwave_decompress_end(begun[i])
+            except (ValueError, RuntimeError) as e:
+                if names is None:
+                    raise
+                raise ValueError(f"{names[i]}: {e}") from e
+        workers = max(1, min(16, int(self.decode_workers)))
+        if self._batch_pool is None or self._batch_pool[0] != workers:
+            self._batch_pool = (workers, ThreadPoolExecutor(max_workers=workers))
+        # the files whose LL part ends first (chroma: a quarter of luma's positions) are finished first
+        first = sorted(range(len(begun)), key=lambda i: begun[i]["shape"][2] * begun[i]["shape"][3])
+        futures = {i: self._batch_pool[1].submit(finish, i) for i in first}
+        out, err = [], None
+        for i in range(len(begun)):
+            try:
+                out.append(futures[i].result())
+            except Exception as e:  # noqa: BLE001 - every thread is waited for before the first failure is reported
+                out.append(None)
+                err = err or e
+        if err is not None:
+            raise err
         for i, t in enumerate(out):
             main.wait_stream(self.side_streams[i])
             t.record_stream(main)
@@ -1314,28 +1355,13 @@ class HipEngine:
 
     def _ll_ar_planes_one_by_one(self, coder, dec, N, H, W, stream):
         """plane order outside the batched form: one single-plane call after the other, the state read back in between"""
-        rules = self._ll_rules(coder, N, H, W)
-        L = _lib.hip()
-        w = self._ll_weights(coder)
-        cdf, sizes, offsets = self._dev_tables("gauss")
-        vp = lambda t: C.c_void_p(t.data_ptr())
+        t = dict(self._ll_ar_ticket(dec, N, H, W, stream), path="per-file")
         with torch.cuda.stream(stream):
-            words = torch.from_numpy(dec.words.copy()).to(self.dev)
-            ll = torch.zeros((N, 1, H, W), dtype=torch.float32, device=self.dev)
-            state = torch.zeros(3, dtype=torch.int64, device=self.dev)
-            keep = [words]
             for p in range(N):
-                x, pos = dec.get_state()
-                scratch = torch.zeros(L.pmctf_ll_ar_scratch_floats(1, H, W), dtype=torch.float32, device=self.dev)
-                keep.append(scratch)
-                _lib.check(L.pmctf_ll_ar_decode_rules_f32(vp(w), vp(words), words.numel(), C.c_uint64(x), pos, vp(cdf),
-                                                          vp(sizes), vp(offsets), cdf.shape[1], float(self.lmin),
-                                                          float(self.lstep), vp(ll[p]), vp(scratch), 1, H, W, vp(state),
-                                                          rules[0], rules[1], rules[2], C.c_void_p(stream.cuda_stream)),
-                           "ll_ar_decode")
-                if p + 1 < N:
-                    self.ll_ar_finish({"dec": dec, "ll": ll, "state": state, "stream": stream})
-        return {"dec": dec, "ll": ll, "state": state, "stream": stream, "keep": keep, "path": "per-file"}
+                if p:
+                    self.ll_ar_finish(t)
+                self._ll_ar_issue(coder, t, t["ll"][p], 1)
+        return t
 
     def pwave_decompress_batch_begin(self, jobs, ll_order="position"):
         """jobs: [(coder, data, padding, q_index, qp_scale)] as for pwave_decompress_many_begin — typically every picture
@@ -1343,25 +1369,13 @@ class HipEngine:
         as ONE series of launches (a workgroup per file) on the group's stream, the others as per-file launches on side
         streams.  ll_order: "position" (files written with ar_order=True) or "plane" (the one-shot order of
         skip_decoding=True).  Finish with pwave_decompress_batch_end."""
-        import struct
         if ll_order not in self.LL_ORDERS:
             raise ValueError(f"ll_order must be one of {sorted(self.LL_ORDERS)}")
         cols = self.tables["gauss"][0].shape[1]
-        begun, groups = [], {}
-        for i, (coder, data, padding, q_index, qp_scale) in enumerate(jobs):
-            if len(data) < 16:
-                raise ValueError("bitstream file shorter than its header")
-            height, width, N = struct.unpack(">III", data[:12])
-            (n,) = struct.unpack(">I", data[12:16])
-            if not (1 <= N <= 4 and height >= 1 and width >= 1 and n >= 1 and len(data) >= 16 + n):
-                raise ValueError("bitstream file with an implausible or truncated header")
-            dec = HostDecoder(self.tables, data[16:16 + n])
-            new_h = (height + padding - 1) // padding * padding
-            new_w = (width + padding - 1) // padding * padding
-            sh, sw = new_h >> self.L, new_w >> self.L
-            form = self.ll_batch_form(N, sw, cols, ll_order, self._ll_rules(coder, N, sh, sw)[0])
-            begun.append({"coder": coder, "dec": dec, "ticket": None, "q": self.q_scales(coder, q_index, qp_scale), "N": N,
-                          "shape": (new_h, new_w, sh, sw)})
+        begun, groups = [self._open_file(*j) for j in jobs], {}
+        for i, b in enumerate(begun):
+            N, (_, _, sh, sw) = b["N"], b["shape"]
+            form = self.ll_batch_form(N, sw, cols, ll_order, self._ll_rules(b["coder"], N, sh, sw)[0])
             groups.setdefault((N, sh, sw, form), []).append(i)
         while len(self.side_streams) < len(jobs):
             self.side_streams.append(torch.cuda.Stream(device=self.dev))
@@ -1388,71 +1402,14 @@ class HipEngine:
         return begun
 
     def pwave_decompress_batch_end(self, begun, names=None):
-        """The four-step parts of the begun files on host threads (self.decode_workers of them), each file on its own
-        stream, as pwave_decompress_many_end does for the files of one pair.  names: one label per file, put in front of
-        the ValueError a damaged file raises."""
-        main = torch.cuda.current_stream(self.dev)
-        ready = torch.cuda.Event()
-        ready.record(main)
-
-        def finish(i):
-            torch.cuda.set_device(self.dev)
-            st = self.side_streams[i]
-            st.wait_event(ready)
-            try:
-                with torch.no_grad(), torch.cuda.stream(st):
-                    return self.pwave_decompress_end(begun[i])
-            except (ValueError, RuntimeError) as e:
-                if names is None:
-                    raise
-                raise ValueError(f"{names[i]}: {e}") from e
-        workers = max(1, min(16, int(self.decode_workers)))
-        if self._batch_pool is None or self._batch_pool[0] != workers:
-            self._batch_pool = (workers, ThreadPoolExecutor(max_workers=workers))
-        # the files whose LL part ends first (chroma: a quarter of luma's positions) are finished first
-        first = sorted(range(len(begun)), key=lambda i: begun[i]["shape"][2] * begun[i]["shape"][3])
-        futures = {i: self._batch_pool[1].submit(finish, i) for i in first}
-        out, err = [], None
-        for i in range(len(begun)):
-            try:
-                out.append(futures[i].result())
-            except Exception as e:  # noqa: BLE001 - every thread is waited for before the first failure is reported
-                out.append(None)
-                err = err or e
-        if err is not None:
-            raise err
-        for i, t in enumerate(out):
-            main.wait_stream(self.side_streams[i])
-            t.record_stream(main)
-        return out
+        """The four-step parts of the begun files, as pwave_decompress_many_end does for the files of one pair.
+        names: one label per file, put in front of the ValueError a damaged file raises."""
+        return self._finish_files(begun, names)
 
     def pwave_decompress_end(self, job):
-        coder, dec, N = job["coder"], job["dec"], job["N"]
-        q_scale, q_scale_ll = job["q"]
-        new_h, new_w, sh, sw = job["shape"]
-        ll_rec = self.ll_ar_finish(job["ticket"])
-        hat = {lvl: {} for lvl in range(self.L)}
-        hat[self.L - 1]["ll"] = ll_rec
-        lstm_state = self.ctx_init(N, sh, sw)
-        context = self.ctx_forward_one_subband(coder, lstm_state, ll_rec, "ll", self.L - 1)
-        for lvl in range(self.L - 1, -1, -1):
-            h, w = new_h >> (lvl + 1), new_w >> (lvl + 1)
-            for sidx, sb in enumerate(("lh", "hl", "hh")):
-                ctx = ops.empty_nhwc(N, h, w, 1, self.dev)
-                ew(EW_COPY, as_nchw(context)[:, sidx:sidx + 1], out=as_nchw(ctx))
-                prev = hat[lvl + 1][sb] if lvl < self.L - 1 else None
-                s_hat = self.fusion_decompress(f"{coder}.context_fusion.{lvl}.{sb}", ctx, prev, dec, N, h, w)
-                hat[lvl][sb] = s_hat
-                context = self.ctx_forward_one_subband(coder, lstm_state, s_hat, sb, lvl)
-        rec_ll = ew(EW_DIVS, hat[self.L - 1]["ll"], alpha=q_scale_ll)
-        out = None
-        for lvl in range(self.L - 1, -1, -1):
-            sbs = {"ll": rec_ll}
-            for sb in ("lh", "hl", "hh"):
-                sbs[sb] = ew(EW_DIVS, hat[lvl][sb], alpha=q_scale)
-            out = self.backward_lift_2d(coder, sbs)
-            rec_ll = out
-        return self.post_process(coder, out, 256.0, 256.0)
+        ll_hat = self.ll_ar_finish(job["ticket"])
+        hat = self.pwave_walk(job["coder"], ll_hat, job["dec"])
+        return self.pwave_synthesis(job["coder"], hat, *job["q"])
 
     def decompress_mv(self, string, height, width, dpb, stage_idx=0, q_index=0, me_downsample=1):
         """pMCTF.decompress_mv (pMCTF_L.py:497-523); height/width: size of the plane motion was estimated on"""
@@ -1466,23 +1423,7 @@ class HipEngine:
         zsym = torch.from_numpy(dec.decode(idx, f"z{s}")).to(self.dev)
         z_hat = ops.sym_to_nhwc(zsym, hz, wz, 64)
         common = self.mv_prior_param_decoder(z_hat, self.to_nhwc_input(dpb["ref_mv_y"]), s)
-        hy, wy = common.shape[1], common.shape[2]
-        so_far = torch.empty((1, hy, wy, 64), dtype=torch.float32, device=self.dev)
-        sp = None
-        for t in range(4):
-            if t > 0:
-                x = self.conv(f"mv_y_spatial_prior_adaptor_{t}.{s}")(self.cat_channels(so_far, common))
-                for i in range(3):
-                    x = self.depth_conv_block(f"mv_y_spatial_prior.{s}.{i}", x)
-                sp = x
-            idx_d = ops.mv_fourpart_indexes(common, sp, hy, wy, t, self.lmin, self.lstep)
-            sym = self._decode(dec, idx_d, "gauss")
-            ops.mv_fourpart_dequant(sym, common, sp, so_far, t)
-        mv_y_hat = ops.mv_dequant(so_far, common)
-        mv_hat, mv_feature = self.mv_dec(s, mv_y_hat, q_dec)
-        if me_downsample > 1:       # :516-517
-            mv_hat = ops.bilinear_up2(mv_hat, float(me_downsample), me_downsample)
-        return {"mv_hat": mv_hat, "mv_feature": mv_feature, "mv_y_hat": mv_y_hat}
+        return self.mv_fourpart(s, common, dec, q_dec, me_downsample)
 
 
 class HostDecoder:

@@ -72,14 +72,12 @@ SITES = [
      "lt_event: the batched luma lifting is done, the next stage's motion chain may read its L_t", "3, 4"),
     ("engine.py", "HipEngine.ll_ar_finish", {"synchronize": 1, "record_stream": 1},
      "the LL decode's side stream is drained before the host reads its coder state; ll goes to the caller's stream", "5, 6"),
-    ("engine.py", "HipEngine.pwave_decompress_many_end", {"record": 1, "wait_stream": 1, "record_stream": 1},
-     "decoded subbands from the side streams back to the caller's stream", "5"),
-    ("engine.py", "HipEngine.pwave_decompress_many_end.finish", {"wait_event": 1},
-     "a side stream waits for what the caller's stream has decoded so far", "5"),
-    ("engine.py", "HipEngine.pwave_decompress_batch_end", {"record": 1, "wait_stream": 1, "record_stream": 1},
-     "a GOP's decoded planes from the side streams (fed by the batch streams) back to the caller's stream", "6"),
-    ("engine.py", "HipEngine.pwave_decompress_batch_end.finish", {"wait_event": 1},
-     "a side stream waits for the caller's stream before a file's remaining subbands", "6"),
+    ("engine.py", "HipEngine._finish_files", {"record": 1, "wait_stream": 1, "record_stream": 1},
+     "decoded subbands from the side streams back to the caller's stream; a GOP's decoded planes from the side streams "
+     "(fed by the batch streams) back to the caller's stream", "5, 6"),
+    ("engine.py", "HipEngine._finish_files.finish", {"wait_event": 1},
+     "a side stream waits for what the caller's stream has decoded so far; a side stream waits for the caller's stream "
+     "before a file's remaining subbands", "5, 6"),
     ("ops.py", "Conv2d.__call__", {"record": 2}, "timing events of the conv probe, on the launch's stream", "2 (probe on)"),
     ("ops.py", "conv_at_class", {"record": 2}, "timing events of the conv probe, on the launch's stream", "2 (probe on)"),
     ("pair_plan.py", "PairPlan._record", {"wait_stream": 2},

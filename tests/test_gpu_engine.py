@@ -1175,6 +1175,39 @@ def test_ll_params_and_conv_lstm_context_bitexact(setup):
             assert_same(st[key][1].permute(0, 3, 1, 2), ost[1], f"{key} cell after {name}{lvl}")
 
 
+@pytest.mark.parametrize("N,H,W", [(2, 6, 10), (1, 5, 7)])
+def test_fusion_body_decodes_what_it_coded(setup, N, H, W):
+    """The four-step fusion body alone, coding and decoding one top-level subband: even sizes take the quarter-position
+    branch, odd sizes the whole-plane branch, which no file of the suite reaches when decoding (every padded subband is
+    even).  The decoder must rebuild the encoder's quantised plane bit for bit from the coded bytes, reading exactly the
+    CDF rows and symbols the encoder wrote."""
+    from pMCTF.hip.engine import HostDecoder, SymbolStream
+
+    class Recording(HostDecoder):
+        def decode(self, idx, table):
+            out = super().decode(idx, table)
+            self.seen = getattr(self, "seen", []) + [(np.array(idx, np.int16).reshape(-1), out.copy())]
+            return out
+    net, _ = setup
+    eng = net.engine()
+    p = "hp_coder.context_fusion.3.lh"
+    g = torch.Generator().manual_seed(1000 * N + 10 * H + W)
+    x = torch.round(8 * torch.randn((N, 1, H, W), generator=g)).cuda()
+    ctx = torch.randn((N, H, W, 1), generator=g).cuda()
+    stream = SymbolStream(4 * N * H * W, eng.dev)
+    coded = eng.fusion(p, ctx, None, stream, N, H, W, x)
+    _, data, (sym, idx) = eng.coder.submit(stream, eng.tables, lambda n: b"", None, keep=True).result()
+    assert sym.size == 4 * N * H * W and len(set(sym.tolist())) > 4, "a stream that exercises the coder"
+    dec = Recording(eng.tables, data)
+    decoded = eng.fusion(p, ctx, None, dec, N, H, W)
+    torch.cuda.synchronize()
+    assert decoded.shape == coded.shape == (N, 1, H, W)
+    assert torch.equal(decoded.view(torch.int32), coded.view(torch.int32)), "decoded plane differs from the coded one"
+    assert_same(np.concatenate([i for i, _ in dec.seen]), idx, "cdf rows")
+    assert_same(np.concatenate([s for _, s in dec.seen]), sym, "symbols")
+    assert float(coded.abs().max()) > 0
+
+
 def test_advance_dpb_equals_encode_one_stage_dpb(cuda):
     """pMCTF.advance_dpb (the motion part of a pair only) hands on exactly the `dpb` that encode_one_stage returns —
     what pair-level sharding rests on.  Two chained pairs, second motion model (stage_idx 1)."""
