@@ -259,7 +259,7 @@ class HipEngine:
             if k.endswith(".mask"):
                 sd[k[:-5] + ".weight"] = sd[k[:-5] + ".weight"] * sd[k]
         self.sd = sd
-        self._cache_lock = threading.Lock()     # creation of the cached device objects below (conv, dwconv, lin_tables)
+        self._cache_lock = threading.Lock()     # creation of every cached device object below: one object per key, ever
         self._convs = {}
         self._dw = {}
         self._lin = {}
@@ -639,13 +639,17 @@ class HipEngine:
         other scalar parameters: rows softplus(h) f1..f4, b f1..f4, tanh(a) f1..f3"""
         c = self._bitparm.get(s)
         if c is None:
-            import torch.nn.functional as F
-            g = lambda i, n: self.sd[f"mv_bit_est.{s}.f{i}.{n}"].reshape(-1)
-            rows = [F.softplus(g(i, "h")) for i in (1, 2, 3, 4)] + [g(i, "b") for i in (1, 2, 3, 4)] + \
-                   [torch.tanh(g(i, "a")) for i in (1, 2, 3)]
-            c = torch.stack(rows).contiguous().to(self.dev)
-            torch.cuda.synchronize(self.dev)
-            self._bitparm[s] = c
+            with self._cache_lock:                      # one object per key, ever (see conv)
+                c = self._bitparm.get(s)
+                if c is not None:
+                    return c
+                import torch.nn.functional as F
+                g = lambda i, n: self.sd[f"mv_bit_est.{s}.f{i}.{n}"].reshape(-1)
+                rows = [F.softplus(g(i, "h")) for i in (1, 2, 3, 4)] + [g(i, "b") for i in (1, 2, 3, 4)] + \
+                       [torch.tanh(g(i, "a")) for i in (1, 2, 3)]
+                c = torch.stack(rows).contiguous().to(self.dev)
+                torch.cuda.synchronize(self.dev)
+                self._bitparm[s] = c
         return c
 
     def compress_mv(self, ref_y, cur_y, dpb, stage_idx=0, q_index=0, estimate=False, me_downsample=1):
@@ -1116,35 +1120,42 @@ class HipEngine:
     def _dev_tables(self, name):
         t = self._dev_tab.get(name)
         if t is None:
-            cdf, sizes, offsets = self.tables[name]
-            t = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.dev) for a in (cdf, sizes, offsets))
-            torch.cuda.synchronize(self.dev)
-            self._dev_tab[name] = t
+            with self._cache_lock:                      # one object per key, ever (see conv)
+                t = self._dev_tab.get(name)
+                if t is None:
+                    cdf, sizes, offsets = self.tables[name]
+                    t = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.dev) for a in (cdf, sizes, offsets))
+                    torch.cuda.synchronize(self.dev)
+                    self._dev_tab[name] = t
         return t
 
     def _ll_weights(self, coder):
         w = self._llw.get(coder)
         if w is None:
-            p = f"{coder}.context_fusion.{self.L - 1}.ll"
-            g = lambda k: np.ascontiguousarray(self.sd[p + k].numpy(), dtype=np.float32)
-            names = [".residualBlocks.0.conv1", ".residualBlocks.0.conv2", ".residualBlocks.1.conv1",
-                     ".residualBlocks.1.conv2", ".maskedConv2"]
-            wb = [g(n + ".weight") for n in names]
-            bb = [g(n + ".bias") for n in names]
-            PF = C.POINTER(C.c_float)
-            wb_p = (C.c_void_p * 5)(*[a.ctypes.data for a in wb])
-            bb_p = (C.c_void_p * 5)(*[a.ctypes.data for a in bb])
-            L = _lib.hip()
-            out = np.empty(L.pmctf_ll_ar_packed_size(), np.float32)
-            keep = [g(".maskedConv1.weight"), g(".maskedConv1.bias"), g(".convs.0.weight"), g(".convs.0.bias"),
-                    g(".convs.1.weight"), g(".convs.1.bias"), g(".convs.2.weight"), g(".convs.2.bias")]
-            _lib.check(L.pmctf_ll_ar_pack_weights(keep[0].ctypes.data, keep[1].ctypes.data, C.addressof(wb_p),
-                                                  C.addressof(bb_p), keep[2].ctypes.data, keep[3].ctypes.data,
-                                                  keep[4].ctypes.data, keep[5].ctypes.data, keep[6].ctypes.data,
-                                                  keep[7].ctypes.data, out.ctypes.data), "ll_ar_pack_weights")
-            w = torch.from_numpy(out).to(self.dev)
-            torch.cuda.synchronize(self.dev)
-            self._llw[coder] = w
+            with self._cache_lock:                      # one object per key, ever (see conv)
+                w = self._llw.get(coder)
+                if w is not None:
+                    return w
+                p = f"{coder}.context_fusion.{self.L - 1}.ll"
+                g = lambda k: np.ascontiguousarray(self.sd[p + k].numpy(), dtype=np.float32)
+                names = [".residualBlocks.0.conv1", ".residualBlocks.0.conv2", ".residualBlocks.1.conv1",
+                         ".residualBlocks.1.conv2", ".maskedConv2"]
+                wb = [g(n + ".weight") for n in names]
+                bb = [g(n + ".bias") for n in names]
+                PF = C.POINTER(C.c_float)
+                wb_p = (C.c_void_p * 5)(*[a.ctypes.data for a in wb])
+                bb_p = (C.c_void_p * 5)(*[a.ctypes.data for a in bb])
+                L = _lib.hip()
+                out = np.empty(L.pmctf_ll_ar_packed_size(), np.float32)
+                keep = [g(".maskedConv1.weight"), g(".maskedConv1.bias"), g(".convs.0.weight"), g(".convs.0.bias"),
+                        g(".convs.1.weight"), g(".convs.1.bias"), g(".convs.2.weight"), g(".convs.2.bias")]
+                _lib.check(L.pmctf_ll_ar_pack_weights(keep[0].ctypes.data, keep[1].ctypes.data, C.addressof(wb_p),
+                                                      C.addressof(bb_p), keep[2].ctypes.data, keep[3].ctypes.data,
+                                                      keep[4].ctypes.data, keep[5].ctypes.data, keep[6].ctypes.data,
+                                                      keep[7].ctypes.data, out.ctypes.data), "ll_ar_pack_weights")
+                w = torch.from_numpy(out).to(self.dev)
+                torch.cuda.synchronize(self.dev)
+                self._llw[coder] = w
         return w
 
     def _decode(self, dec, idx_dev, table):
