@@ -973,17 +973,22 @@ class HipEngine:
             return x_hat, stream, hat
         return x_hat, stream
 
-    def pwave_walk(self, coder, ll_hat, io, coded=lambda lvl, sb: None):
+    def pwave_walk(self, coder, ll_hat, io, coded=lambda lvl, sb: None, stop_level=0):
         """The subbands below the LL subband, levels L-1..0 and lh, hl, hh in coding order (pWave.py:381-463, 467-529):
         the ONE walk the encoder, the estimator and the decoder make.  ll_hat: the quantised LL plane (N,1,h,w), which
         fixes the geometry of every level; io: SymbolStream, BitSink or HostDecoder; coded(lvl, sb): the plane to code
-        (an encoder's; launched between the context slice and the fusion).  Returns hat[lvl][sb]."""
+        (an encoder's; launched between the context slice and the fusion).  Returns hat[lvl][sb].
+        stop_level=k > 0 (a decoder's): the walk ends with the hh subband of level k, whose context update
+        nobody reads; hat[lvl] is empty below k, and for k = L nothing runs at all.  What is decoded is a prefix of the
+        full walk's launches and symbols."""
         N = ll_hat.shape[0]
         hat = {lvl: {} for lvl in range(self.L)}
         hat[self.L - 1]["ll"] = ll_hat
+        if stop_level >= self.L:
+            return hat
         lstm_state = self.ctx_init(N, ll_hat.shape[2], ll_hat.shape[3])
         context = self.ctx_forward_one_subband(coder, lstm_state, ll_hat, "ll", self.L - 1)
-        for lvl in range(self.L - 1, -1, -1):
+        for lvl in range(self.L - 1, stop_level - 1, -1):
             for sidx, sb in enumerate(("lh", "hl", "hh")):
                 h, w = context.shape[1], context.shape[2]
                 ctx = ops.empty_nhwc(N, h, w, 1, self.dev)
@@ -991,20 +996,25 @@ class HipEngine:
                 prev = hat[lvl + 1][sb] if lvl < self.L - 1 else None
                 s_hat = self.fusion(f"{coder}.context_fusion.{lvl}.{sb}", ctx, prev, io, N, h, w, coded(lvl, sb))
                 hat[lvl][sb] = s_hat
+                if stop_level > 0 and lvl == stop_level and sb == "hh":
+                    break
                 context = self.ctx_forward_one_subband(coder, lstm_state, s_hat, sb, lvl)
         return hat
 
-    def pwave_synthesis(self, coder, hat, q_scale, q_scale_ll):
-        """dequantise, inverse DWT, post-process (pWave.py:446-455; the tail of pWave.decompress)"""
-        out = None
+    def pwave_synthesis(self, coder, hat, q_scale, q_scale_ll, level=0):
+        """dequantise, inverse DWT, post-process (pWave.py:446-455; the tail of pWave.decompress).
+        level=k > 0: the inverse DWT stops after level k and its LL band (N,1,H>>k,W>>k) is returned times
+        2^-k, the low band's DC gain of 2 per 2-D level taken out; the post-processing network, a full-resolution
+        stage, is not applied."""
         rec_ll = ew(EW_DIVS, hat[self.L - 1]["ll"], alpha=q_scale_ll)
-        for lvl in range(self.L - 1, -1, -1):
+        for lvl in range(self.L - 1, level - 1, -1):
             sbs = {"ll": rec_ll}
             for sb in ("lh", "hl", "hh"):
                 sbs[sb] = ew(EW_DIVS, hat[lvl][sb], alpha=q_scale)
-            out = self.backward_lift_2d(coder, sbs)
-            rec_ll = out
-        return self.post_process(coder, out, 256.0, 256.0)
+            rec_ll = self.backward_lift_2d(coder, sbs)
+        if level > 0:
+            return ew(EW_MULS, rec_ll, alpha=2.0 ** -level)
+        return self.post_process(coder, rec_ll, 256.0, 256.0)
 
     # ------------------------------------------------------------------ estimate-mode stage (pMCTF_L.py:332-379)
     def forward_one_stage(self, ref, cur, q_index, code_lt, dpb, mv_hat=None, stage_idx=0, me_downsample=1):
@@ -1220,10 +1230,14 @@ class HipEngine:
     def ll_ar_decode(self, coder, dec, N, H, W):
         return self.ll_ar_finish(self.ll_ar_launch(coder, dec, N, H, W))
 
-    def _open_file(self, coder, data, padding, q_index, qp_scale=None):
+    def _open_file(self, coder, data, padding, q_index, qp_scale=None, level=0):
         """One bitstream file -> its `begun` record, the LL decode not yet started (ticket None).  A file that is too
-        short for its header or its payload, or whose header is implausible, raises ValueError."""
+        short for its header or its payload, or whose header is implausible, raises ValueError.
+        level: the spatial level 0..L the file is decoded at (pwave_decompress_end); the record carries it, and once
+        the file is finished "symbols_decoded" and "payload_bytes_used" as well."""
         import struct
+        if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= self.L:
+            raise ValueError(f"the spatial level is an integer from 0 to {self.L} (got {level!r})")
         if len(data) < 16:
             raise ValueError("bitstream file shorter than its header")
         height, width, N = struct.unpack(">III", data[:12])
@@ -1234,28 +1248,29 @@ class HipEngine:
         new_h = (height + padding - 1) // padding * padding
         new_w = (width + padding - 1) // padding * padding
         return {"coder": coder, "dec": dec, "ticket": None, "q": self.q_scales(coder, q_index, qp_scale), "N": N,
-                "shape": (new_h, new_w, new_h >> self.L, new_w >> self.L)}
+                "shape": (new_h, new_w, new_h >> self.L, new_w >> self.L), "level": level, "payload_bytes": n}
 
-    def pwave_decompress_begin(self, coder, data, padding, q_index, qp_scale=None, stream=None):
+    def pwave_decompress_begin(self, coder, data, padding, q_index, qp_scale=None, stream=None, level=0):
         """Parse one bitstream file and start its sequential LL decode; finish with pwave_decompress_end."""
-        b = self._open_file(coder, data, padding, q_index, qp_scale)
+        b = self._open_file(coder, data, padding, q_index, qp_scale, level)
         b["ticket"] = self.ll_ar_launch(coder, b["dec"], b["N"], b["shape"][2], b["shape"][3], stream)
         return b
 
-    def pwave_decompress(self, coder, data, padding, q_index, qp_scale=None):
-        """pWave.decompress (pWave.py:467-529) from the bytes of one bitstream file -> x_hat plane (N,1,Hp,Wp)"""
-        return self.pwave_decompress_end(self.pwave_decompress_begin(coder, data, padding, q_index, qp_scale))
+    def pwave_decompress(self, coder, data, padding, q_index, qp_scale=None, level=0):
+        """pWave.decompress (pWave.py:467-529) from the bytes of one bitstream file -> x_hat plane (N,1,Hp,Wp);
+        level=k: the plane of spatial level k, (N,1,Hp>>k,Wp>>k) (pwave_decompress_end)"""
+        return self.pwave_decompress_end(self.pwave_decompress_begin(coder, data, padding, q_index, qp_scale, level=level))
 
-    def pwave_decompress_many(self, jobs):
+    def pwave_decompress_many(self, jobs, level=0):
         """jobs: [(coder, data, padding, q_index, qp_scale)].  All LL decodes run concurrently on side streams."""
-        return self.pwave_decompress_many_end(self.pwave_decompress_many_begin(jobs))
+        return self.pwave_decompress_many_end(self.pwave_decompress_many_begin(jobs, level))
 
-    def pwave_decompress_many_begin(self, jobs):
+    def pwave_decompress_many_begin(self, jobs, level=0):
         """Parse the files and start their sequential LL decodes (side streams); the caller may do other work — the
         motion stream's decode — before pwave_decompress_many_end."""
         while len(self.side_streams) < len(jobs):
             self.side_streams.append(torch.cuda.Stream(device=self.dev))
-        return [self.pwave_decompress_begin(*j, stream=self.side_streams[i]) for i, j in enumerate(jobs)]
+        return [self.pwave_decompress_begin(*j, stream=self.side_streams[i], level=level) for i, j in enumerate(jobs)]
 
     def pwave_decompress_many_end(self, begun):
         if len(begun) == 1:         # one file: on the caller's stream, no thread
@@ -1374,16 +1389,16 @@ class HipEngine:
                 self._ll_ar_issue(coder, t, t["ll"][p], 1)
         return t
 
-    def pwave_decompress_batch_begin(self, jobs, ll_order="position"):
+    def pwave_decompress_batch_begin(self, jobs, ll_order="position", level=0):
         """jobs: [(coder, data, padding, q_index, qp_scale)] as for pwave_decompress_many_begin — typically every picture
         file of a GOP.  The files are grouped by geometry; the sequential LL parts of a group the batched form covers run
         as ONE series of launches (a workgroup per file) on the group's stream, the others as per-file launches on side
         streams.  ll_order: "position" (files written with ar_order=True) or "plane" (the one-shot order of
-        skip_decoding=True).  Finish with pwave_decompress_batch_end."""
+        skip_decoding=True).  level: the spatial level every file is decoded at.  Finish with pwave_decompress_batch_end."""
         if ll_order not in self.LL_ORDERS:
             raise ValueError(f"ll_order must be one of {sorted(self.LL_ORDERS)}")
         cols = self.tables["gauss"][0].shape[1]
-        begun, groups = [self._open_file(*j) for j in jobs], {}
+        begun, groups = [self._open_file(*j, level=level) for j in jobs], {}
         for i, b in enumerate(begun):
             N, (_, _, sh, sw) = b["N"], b["shape"]
             form = self.ll_batch_form(N, sw, cols, ll_order, self._ll_rules(b["coder"], N, sh, sw)[0])
@@ -1418,9 +1433,16 @@ class HipEngine:
         return self._finish_files(begun, names)
 
     def pwave_decompress_end(self, job):
+        """The rest of a begun file at its spatial level k: the walk for the levels L-1..k, the synthesis stopped after
+        level k.  Nothing behind the last subband of level k is read from the stream.  The record then says what was
+        read: "symbols_decoded", the LL positions of the sequential decode plus every size passed to
+        HostDecoder.decode, and "payload_bytes_used", the decoder's position (get_state) in bytes of the payload."""
+        level = job["level"]
         ll_hat = self.ll_ar_finish(job["ticket"])
-        hat = self.pwave_walk(job["coder"], ll_hat, job["dec"])
-        return self.pwave_synthesis(job["coder"], hat, *job["q"])
+        hat = self.pwave_walk(job["coder"], ll_hat, job["dec"], stop_level=level)
+        job["symbols_decoded"] = ll_hat.numel() + job["dec"].symbols
+        job["payload_bytes_used"] = min(1 + 4 * job["dec"].get_state()[1], job["payload_bytes"])
+        return self.pwave_synthesis(job["coder"], hat, *job["q"], level=level)
 
     def decompress_mv(self, string, height, width, dpb, stage_idx=0, q_index=0, me_downsample=1):
         """pMCTF.decompress_mv (pMCTF_L.py:497-523); height/width: size of the plane motion was estimated on"""
@@ -1447,6 +1469,7 @@ class HostDecoder:
         buf = np.frombuffer(bytes(stream), dtype=np.uint8).copy()
         _lib.check(self.R.pmctf_rans_decoder_set_stream(self.h, buf.ctypes.data, buf.size), "rans set_stream")
         self.words = np.frombuffer(buf[1:].tobytes(), dtype=np.uint32)       # payload words after the flag byte
+        self.symbols = 0                                                     # sizes passed to decode, summed
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -1457,6 +1480,7 @@ class HostDecoder:
         idx = np.ascontiguousarray(idx, dtype=np.int16).reshape(-1)
         cdf, sizes, offsets = self.tables[table]
         out = np.empty(idx.size, np.int16)
+        self.symbols += idx.size
         _lib.check(self.R.pmctf_rans_decoder_decode_stream(self.h, idx.ctypes.data, idx.size, cdf.ctypes.data,
                                                            cdf.shape[0], cdf.shape[1], sizes.ctypes.data,
                                                            offsets.ctypes.data, out.ctypes.data), "rans decode_stream")

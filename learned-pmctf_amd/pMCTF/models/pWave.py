@@ -113,13 +113,14 @@ class pWave(nn.Module):
         return x_hat
 
     @torch.no_grad()
-    def decompress(self, file_name, padding=64, q_index=None, qp_scale=None):
-        """pWave.py:466-529"""
+    def decompress(self, file_name, padding=64, q_index=None, qp_scale=None, spatial_level=0):
+        """pWave.py:466-529.  spatial_level=k: the picture at 1/2^k of its size from the coarse subbands alone,
+        (N,1,Hp>>k,Wp>>k), nothing behind level k read from the stream (HipEngine.pwave_decompress_end)"""
         eng = self.engine()
         with open(file_name, "rb") as f:
             data = f.read()
         qs = None if qp_scale is None else float(qp_scale)
-        x_hat = eng.pwave_decompress("coder", data, padding, q_index, qs)
+        x_hat = eng.pwave_decompress("coder", data, padding, q_index, qs, level=spatial_level)
         if x_hat.shape[0] == 3:
             x_hat = torch.cat([x_hat[c:c + 1] for c in range(3)], dim=1)
         return {"x_hat": x_hat}

@@ -314,15 +314,16 @@ class pMCTF(nn.Module):
 
     @torch.no_grad()
     @_gated
-    def decompress_one_stage(self, file_name, code_lt, ischroma, psize=128, q_index=0, stage_idx=0):
-        """pMCTF_L.py:422-439"""
-        return self._decompress_files([(file_name, ischroma)], code_lt, psize, q_index, stage_idx)[0]
+    def decompress_one_stage(self, file_name, code_lt, ischroma, psize=128, q_index=0, stage_idx=0, spatial_level=0):
+        """pMCTF_L.py:422-439; spatial_level=k: the planes of spatial level k (HipEngine.pwave_decompress_end)"""
+        return self._decompress_files([(file_name, ischroma)], code_lt, psize, q_index, stage_idx, spatial_level)[0]
 
-    def _decompress_files(self, files, code_lt, psize, q_index, stage_idx):
+    def _decompress_files(self, files, code_lt, psize, q_index, stage_idx, spatial_level=0):
         """H (and L) files of the given (file_name, ischroma) entries; their sequential LL parts decode concurrently"""
-        return self._decompress_files_end(self._decompress_files_begin(files, code_lt, psize, q_index, stage_idx))
+        return self._decompress_files_end(self._decompress_files_begin(files, code_lt, psize, q_index, stage_idx,
+                                                                       spatial_level))
 
-    def _decompress_files_begin(self, files, code_lt, psize, q_index, stage_idx):
+    def _decompress_files_begin(self, files, code_lt, psize, q_index, stage_idx, spatial_level=0):
         """read the files and start their sequential LL decodes on side streams (finish with _decompress_files_end)"""
         from pMCTF.hip.engine import get_curr_q
         self.flush()            # the files of deferred pairs must exist before they are read
@@ -337,7 +338,7 @@ class pMCTF(nn.Module):
                 file_name_l = file_name.replace(osp.basename(file_name), "0_C_main.bin" if ischroma else "0_main.bin")
                 with open(file_name_l, "rb") as f:
                     jobs.append(("lp_coder", f.read(), pad, q_index, None))
-        return files, code_lt, eng.pwave_decompress_many_begin(jobs)
+        return files, code_lt, eng.pwave_decompress_many_begin(jobs, spatial_level)
 
     def _decompress_files_end(self, begun):
         files, code_lt, jobs = begun
@@ -353,17 +354,21 @@ class pMCTF(nn.Module):
 
     @torch.no_grad()
     @_gated
-    def decompress_gop_files(self, files, psize=128, q_index=0, ll_order="position"):
+    def decompress_gop_files(self, files, psize=128, q_index=0, ll_order="position", spatial_level=0):
         """Picture files of any number of pairs and stages in one call.  files: [(data, ischroma, low, stage_idx)] — the
         bytes of one file, whether it holds the two chroma planes, whether it is an L file (lp_coder) or an H file
         (hp_coder, de-quantised with stage_idx's scale).  Returns the x_hat planes in the order of `files`.
-        ll_order: see HipEngine.pwave_decompress_batch_begin."""
-        return self._decompress_gop_files_end(self._decompress_gop_files_begin(files, psize, q_index, ll_order))
+        ll_order: see HipEngine.pwave_decompress_batch_begin.  spatial_level=k: every plane at spatial level k,
+        1/2^k of its size (HipEngine.pwave_decompress_end)."""
+        return self._decompress_gop_files_end(self._decompress_gop_files_begin(files, psize, q_index, ll_order,
+                                                                               spatial_level=spatial_level))
 
     @torch.no_grad()
     @_gated
-    def _decompress_gop_files_begin(self, files, psize, q_index, ll_order, names=None):
-        """start the sequential LL decodes of all files (batched per geometry); finish with _decompress_gop_files_end"""
+    def _decompress_gop_files_begin(self, files, psize, q_index, ll_order, names=None, spatial_level=0):
+        """start the sequential LL decodes of all files (batched per geometry); finish with _decompress_gop_files_end.
+        The first entry of what it returns is the list of the engine's records, one per file in order, which hold
+        "symbols_decoded" and "payload_bytes_used" once the files are finished."""
         from pMCTF.hip.engine import get_curr_q
         self.flush()
         eng = self.engine()
@@ -374,7 +379,7 @@ class pMCTF(nn.Module):
             if not low and self.quant_stage:
                 qp_scale = get_curr_q(eng.sd[f"hp_q_scale.{stage_idx}"], q_index)
             jobs.append(("lp_coder" if low else "hp_coder", data, pad, q_index, qp_scale))
-        return eng.pwave_decompress_batch_begin(jobs, ll_order), names
+        return eng.pwave_decompress_batch_begin(jobs, ll_order, spatial_level), names
 
     @torch.no_grad()
     @_gated

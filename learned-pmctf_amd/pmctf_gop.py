@@ -1187,6 +1187,11 @@ class FullDecode:
     def check_folder(self, bin_folder):
         """refusals that need the folder, raised once its header is read"""
 
+    def picture_size(self, bin_folder, h, w, coded_size_output, coded_format_output):
+        """-> (height, width) of the decoded pictures, the coded size here; a mode that decodes at another size
+        (pmctf_layers.LayerDecode at a spatial level) raises its refusals that need the size, before the codec is looked at"""
+        return h, w
+
     def open(self, bin_folder, header, gops, verify):
         if verify is not False and (verify != "auto" or os.path.exists(os.path.join(bin_folder, PICTURE_HASHES))):
             full = read_picture_hashes(bin_folder, header["frame_num"])
@@ -1220,6 +1225,7 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
         raise ValueError("nothing to write: give yuv_out, png_out or both")
     header, gops = sequence_layout(bin_folder)
     mode.check_folder(bin_folder)
+    ph, pw = mode.picture_size(bin_folder, header["height"], header["width"], coded_size_output, coded_format_output)
     bitdepth = read_picture_format(bin_folder)
     if bitdepth > 8 and png_out is not None:
         raise ValueError(f"{os.path.join(bin_folder, PICTURE_FORMAT)}: the pictures have {bitdepth} bits, png_out writes "
@@ -1231,6 +1237,10 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
     mode.open(bin_folder, header, gops, verify)
     h, w = header["height"], header["width"]
     sink = picture_sink(bin_folder, yuv_out, w, h, dev, bitdepth, coded_size_output, coded_format_output)
+    if (ph, pw) != (h, w):                                                # the coded form at another size: validated above
+        import pmctf_chroma
+        sink = pmctf_chroma.output_format(bin_folder, yuv_out, pw, ph, None, dev, bitdepth, coded_format_output) \
+            or PlainSink(ph, pw, bitdepth)
     if output_layout is not None:
         import pmctf_layout
         sink = pmctf_layout.PackedSink(sink, output_layout, yuv_out, bitdepth)
@@ -1247,7 +1257,7 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
                                                      header["ll_order"])
             source = [first + t for t in offsets]                         # the source index of every decoded picture
             if mode.hash_level is not None:
-                got = picture_hashes(frames, h, w, mode.hash_level, bitdepth)
+                got = picture_hashes(frames, ph, pw, mode.hash_level, bitdepth)
                 bad = []
                 for t, a, b in zip(source, got, mode.recorded(first, size, len(times), len(source))):
                     bad += compare_hash_records([a], [b], t, gop=k, folder=folder)   # per source frame

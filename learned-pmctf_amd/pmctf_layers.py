@@ -18,6 +18,7 @@ The plan, the hash record and extract_layer need no GPU; the decoders have no CP
 import os
 
 import pmctf_gop
+import pmctf_spatial
 from pmctf_records import is_int, read_record, write_record
 
 LAYER_HASHES = "layer_hashes.json"
@@ -90,10 +91,12 @@ def layer_bytes(bin_folder, level, motion_fill=False):
 
 # ---------------------------------------------------------------------------------------------------------------- one GOP
 def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, kk,
-                    motion_fill):
+                    motion_fill, spatial_level=0, counters=None):
     """decode_gop_files up to the synthesis, on the files of layer_file_names alone -> (frames_coded with None where
     nothing was read, names read, bytes read).  The header checks, the one picture batch and the motion loop under it are
-    those of pmctf_gop.decode_gop_files."""
+    those of pmctf_gop.decode_gop_files.  spatial_level=k: the planes of every picture file at spatial level k (the
+    motion fields stay as coded: reduce_motion).  counters: a dict that receives, per picture file name, what the engine
+    says it read of it: {"symbols_decoded", "payload_bytes_used"}."""
     import struct
     import torch
     pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
@@ -132,7 +135,7 @@ def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psiz
     picture(L_FILES[0], False, True, 0, (0, 0))
     picture(L_FILES[1], True, True, 0, (0, 1))
 
-    begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, paths)
+    begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, paths, spatial_level=spatial_level)
     frames_coded = [[None, None, None] for _ in range(gop)]
     dpb, at_stage = None, None
     try:
@@ -151,7 +154,21 @@ def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psiz
         planes = codec._decompress_gop_files_end(begun)
     for (i, c), plane in zip(slots, planes):
         frames_coded[i][c] = plane
+    if counters is not None:
+        for path, job in zip(paths, begun[0]):
+            counters[os.path.basename(path)] = {key: job[key] for key in ("symbols_decoded", "payload_bytes_used")}
     return frames_coded, read, nbytes
+
+
+def reduce_motion(frames_coded, spatial_level):
+    """the motion fields of a GOP's entries for planes of spatial level k: each reduced k times by ops.bilinear_down2(., 2.0),
+    which halves the size and the vectors, so that every vector contributes; once per pair, shared by luma (as it is) and
+    chroma (inverse_MCTF(downscale=True) reduces it once more, as at full size).  Modifies and returns frames_coded."""
+    from pMCTF.hip import ops
+    for entry in frames_coded:
+        for _ in range(spatial_level if entry[2] is not None else 0):
+            entry[2] = ops.bilinear_down2(entry[2].contiguous(), 2.0)
+    return frames_coded
 
 
 def _synthesis(codec, frames_coded, stages, down_to, snapshots=None):
@@ -179,8 +196,9 @@ def _synthesis(codec, frames_coded, stages, down_to, snapshots=None):
     return frames_coded
 
 
-def _check_decode_args(level, motion_fill, ll_order=None):
+def _check_decode_args(level, motion_fill, ll_order=None, spatial_level=0):
     check_level(level)
+    pmctf_spatial.check_spatial_level(spatial_level)
     if not any(motion_fill is v for v in (True, False)):
         raise ValueError(f"motion_fill is True or False (got {motion_fill!r})")
     if ll_order is not None and ll_order not in pmctf_gop.LL_ORDERS:
@@ -199,16 +217,33 @@ def decode_gop_files_layer(codec, bin_folder, gop, pic_height, pic_width, q_inde
     motion_fill=True: full-rate output from the same picture files.  The motion of the stages < kk is decoded too, the H
     planes of those stages are zero tensors, and the result is exactly pmctf_gop.decode_gop of those inputs: every picture
     of the GOP.
+    pmctf_spatial.decode_gop_files_layer(..., spatial_level=k) is this function at 1/2^k of the picture size.
     Returns {"frames": [[Y, UV, None]] (padded), "times": their offsets within the GOP, "frames_coded": the decoded
-    entries the synthesis consumed ([None, None, None] where nothing was read; zero H planes under motion_fill), "stages":
-    S, "files": the names read, in order, "bytes_read": their sizes summed}."""
+    entries the synthesis consumed ([None, None, None] where nothing was read; zero H planes under motion_fill; the motion
+    as reduced), "stages": S, "files": the names read, in order, "bytes_read": their sizes summed, "spatial_level",
+    "size": (height, width) of the pictures, "symbols_decoded" and "payload_bytes_used": per picture file name what the
+    engine decoded of it and how far into its payload it read}."""
+    return _decode_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, level, psize, me_downsample, ll_order,
+                             motion_fill, 0)
+
+
+def _decode_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, level, psize, me_downsample, ll_order,
+                      motion_fill, spatial_level):
+    """decode_gop_files_layer, and at spatial_level=k > 0 (pmctf_spatial) the same loop at 1/2^k of the size:
+    every picture file is decoded at spatial level k (nothing behind its level-k subbands is read from the stream), the
+    motion fields are reduced k times (reduce_motion) and the synthesis runs on the reduced planes; the pictures are padded
+    planes of 1/2^k of the size, to be cropped to pmctf_spatial.spatial_size.  A size that does not offer the level raises
+    the ValueError of spatial_size before any file is opened."""
     import torch
-    _check_decode_args(level, motion_fill, ll_order)
+    _check_decode_args(level, motion_fill, ll_order, spatial_level)
+    size = pmctf_spatial.spatial_size(pic_height, pic_width, spatial_level)
     stages = gop_stages(gop)
     kk = min(level, stages)
+    counters = {}
     with torch.no_grad():
         frames_coded, read, nbytes = _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize,
-                                                     me_downsample, ll_order, kk, motion_fill)
+                                                     me_downsample, ll_order, kk, motion_fill, spatial_level, counters)
+        reduce_motion(frames_coded, spatial_level)
         if motion_fill:
             for stage, _, i_cur in (pmctf_gop.gop_pairs(gop) if gop != 1 else []):
                 if stage < kk:
@@ -222,7 +257,10 @@ def decode_gop_files_layer(codec, bin_folder, gop, pic_height, pic_width, q_inde
             _synthesis(codec, frames_coded, stages, kk)
             times = [j << kk for j in range(gop >> kk)]
             rec = [frames_coded[t] for t in times]
-    return {"frames": rec, "times": times, "frames_coded": coded, "stages": stages, "files": read, "bytes_read": nbytes}
+    return {"frames": rec, "times": times, "frames_coded": coded, "stages": stages, "files": read, "bytes_read": nbytes,
+            "spatial_level": spatial_level, "size": size,
+            "symbols_decoded": {n: c["symbols_decoded"] for n, c in counters.items()},
+            "payload_bytes_used": {n: c["payload_bytes_used"] for n, c in counters.items()}}
 
 
 # ------------------------------------------------------------------------------------------------------------ layer hashes
@@ -349,8 +387,8 @@ def _check_against_extract(bin_folder, level, motion_fill):
 
 def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     """Copy what a level-`level` decode of the sequence in src_folder reads into dst_folder (created when missing; refused
-    when not empty): the header, picture_format.json, display_format.json, source_format.json and layer_hashes.json where
-    present, per GOP
+    when not empty): the header, picture_format.json, display_format.json, source_format.json, layer_hashes.json and
+    spatial_hashes.json where present, per GOP
     exactly layer_file_names(size, level, motion_fill), and layer_extract.json {"format_version", "min_level": level, "motion":
     motion_fill}, which decode_sequence_layer reads.  picture_hashes.json is not copied: the folder cannot produce those
     pictures.  No codec, no GPU.  -> the relative paths written, sorted."""
@@ -364,7 +402,7 @@ def extract_layer(src_folder, dst_folder, level, motion_fill=False):
     import pmctf_chroma
     import pmctf_scale
     copies = [n for n in (G.GOP_STRUCTURE, G.SEQUENCE_HEADER, G.PICTURE_FORMAT, pmctf_scale.DISPLAY_FORMAT,
-                          pmctf_chroma.SOURCE_FORMAT, LAYER_HASHES)
+                          pmctf_chroma.SOURCE_FORMAT, LAYER_HASHES, pmctf_spatial.SPATIAL_HASHES)
               if os.path.exists(os.path.join(src_folder, n))]
     for k, g in enumerate(gops):
         copies += [os.path.join(G.gop_folder(k), n) for n in layer_file_names(g[1], level, motion_fill)]
@@ -385,40 +423,73 @@ class LayerDecode(pmctf_gop.FullDecode):
     """pmctf_gop.decode_sequence_with at a temporal level: every GOP through decode_gop_files_layer, the pictures checked
     against picture_hashes.json where they are the full-rate ones (level 0, or a sequence of lone pictures: exactly
     FullDecode's record) and against layer_hashes.json above; never under motion_fill.  The result gains "level", "times"
-    and "bytes_read"."""
+    and "bytes_read".
+    spatial_level=k > 0: the pictures have pmctf_spatial.spatial_size and are checked against the record of (k, level) in
+    spatial_hashes.json; the refusals that need no codec (a size that does not offer the level, a display form the reduced
+    pictures cannot be given, verify=True without the record) are raised before the codec is looked at.  The result
+    gains "spatial_level", "size" and, per GOP, "symbols_decoded" and "payload_bytes_used" per picture file."""
 
-    def __init__(self, level, motion_fill=False):
-        _check_decode_args(level, motion_fill)
-        self.level, self.motion_fill = level, motion_fill
+    def __init__(self, level, motion_fill=False, spatial_level=0):
+        _check_decode_args(level, motion_fill, spatial_level=spatial_level)
+        self.level, self.motion_fill, self.spatial_level = level, motion_fill, spatial_level
+        self.verify, self.size, self.counters = "auto", None, {"symbols_decoded": [], "payload_bytes_used": []}
 
     def refuse(self, verify):
         if self.motion_fill and verify is True:
             raise ValueError("motion_fill output is never verified: there is no record of it (verify=True refused)")
+        self.verify = verify
 
     def check_folder(self, bin_folder):
         _check_against_extract(bin_folder, self.level, self.motion_fill)
 
+    def picture_size(self, bin_folder, h, w, coded_size_output, coded_format_output):
+        self.size = pmctf_spatial.spatial_size(h, w, self.spatial_level)
+        if self.spatial_level:
+            import pmctf_chroma
+            import pmctf_scale
+            source = pmctf_chroma.read_source_format(bin_folder)
+            other_format = source is not None and source["chroma_format"] != "420"
+            for name, differs, coded in ((pmctf_scale.DISPLAY_FORMAT, True, coded_size_output),
+                                         (pmctf_chroma.SOURCE_FORMAT, other_format, coded_format_output)):
+                path = os.path.join(bin_folder, name)
+                if os.path.exists(path) and differs and not coded:
+                    raise ValueError(f"{path}: the folder's pictures are displayed in another form than they are coded in; "
+                                     f"spatial level {self.spatial_level} gives the coded form alone (ask for the coded "
+                                     f"size and the coded format), resampling a reduced picture is not done")
+            path = os.path.join(bin_folder, pmctf_spatial.SPATIAL_HASHES)
+            if self.verify is True and not os.path.exists(path):
+                raise ValueError(f"{path}: missing (write_spatial_hashes was not run on the folder)")
+        return self.size
+
     def open(self, bin_folder, header, gops, verify):
         top = _max_level(gops)
-        self.full_rate = self.level == 0 or top == 0   # a sequence of lone pictures has one layer, the full-rate one
+        self.full_rate = (self.level == 0 or top == 0) and not self.spatial_level   # lone pictures: one layer, the full-rate one
         if self.motion_fill or verify is False:
             return
-        if self.full_rate:
+        if self.spatial_level:
+            if verify != "auto" or os.path.exists(os.path.join(bin_folder, pmctf_spatial.SPATIAL_HASHES)):
+                rec = pmctf_spatial.read_spatial_hashes(bin_folder)
+                self.frames = rec["layers"][str(self.spatial_level)][str(min(self.level, top))]
+                self.hash_level = rec["level"]
+        elif self.full_rate:
             super().open(bin_folder, header, gops, verify)
         elif verify != "auto" or os.path.exists(_layer_path(bin_folder)):
             layers = read_layer_hashes(bin_folder)
             self.frames, self.hash_level = layers["layers"][str(min(self.level, top))], layers["level"]
 
     def decode_gop(self, codec, folder, size, h, w, q_index, psize, me_downsample, ll_order):
-        out = decode_gop_files_layer(codec, folder, size, h, w, q_index, self.level, psize=psize, me_downsample=me_downsample,
-                                     ll_order=ll_order, motion_fill=self.motion_fill)
+        out = _decode_gop_layer(codec, folder, size, h, w, q_index, self.level, psize, me_downsample, ll_order,
+                                self.motion_fill, self.spatial_level)
+        for key, per_gop in self.counters.items():
+            per_gop.append(out[key])
         return out["frames"], out["times"], out["bytes_read"]
 
     def recorded(self, first, size, at, n):
         return super().recorded(first, size, at, n) if self.full_rate else self.frames[at:at + n]
 
     def result(self, times, nbytes):
-        return {"level": self.level, "times": times, "bytes_read": nbytes}
+        return dict({"level": self.level, "times": times, "bytes_read": nbytes, "spatial_level": self.spatial_level,
+                     "size": self.size}, **self.counters)
 
 
 def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_out=None, verify="auto", motion_fill=False):
@@ -437,6 +508,10 @@ def decode_sequence_layer(codec, bin_folder, yuv_out, level, device=None, png_ou
     decode_sequence_checked does; pmctf_scale.decode_sequence_layer(..., coded_size_output=True) writes them
     as coded.  A source_format.json and a yuv_out ending in .y4m are honoured as decode_sequence_checked honours them
     (pmctf_chroma.decode_sequence_layer(..., coded_format_output=True): the coded 4:2:0 pictures).
+    pmctf_spatial.decode_sequence_layer(..., spatial_level=k) is this function at 1/2^k of the picture size.
     Returns decode_sequence's dict ("frames", "seconds", "verified", "hash_mismatches", "header", "bitdepth") plus "level",
-    "times": the source index of every written picture, and "bytes_read": the sizes of the files read, layer_bytes."""
+    "times": the source index of every written picture, "bytes_read": the sizes of the files read, layer_bytes,
+    "spatial_level", "size": (height, width) of the decoded pictures (the coded size here), and "symbols_decoded" and
+    "payload_bytes_used": per GOP, per picture file name, the symbols the engine decoded and how many bytes of the payload
+    it read."""
     return pmctf_gop.decode_sequence_with(LayerDecode(level, motion_fill), codec, bin_folder, yuv_out, device, png_out, verify)

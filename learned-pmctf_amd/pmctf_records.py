@@ -1,6 +1,6 @@
 """The sidecar records of a bitstream folder (sequence.json, picture_format.json, picture_hashes.json, gop_structure.json,
-rate_control.json, layer_hashes.json, layer_extract.json, display_format.json, source_format.json): the one place that
-reads and writes them as JSON.  Every record is an object with a "format_version"; what its other fields mean is checked
+rate_control.json, layer_hashes.json, spatial_hashes.json, layer_extract.json, display_format.json, source_format.json):
+the one place that reads and writes them as JSON.  Every record is an object with a "format_version"; what its other fields mean is checked
 by the module that owns it.  Standard library only."""
 import json
 

@@ -25,6 +25,11 @@ A folder coded from a .y4m or from a 4:2:2 / 4:4:4 source (it holds source_forma
 its source, converted on the GPU after the resampling (pmctf_chroma); --coded-format-output writes the coded
 4:2:0 pictures instead.  An OUT path ending in .y4m becomes a Y4M file (its F tag is the recorded frame rate, 25:1 when
 there is none).
+--spatial-level K (pmctf_spatial.decode_sequence_layer) decodes every picture at 1/2^K of its size from the
+coarse subbands of the same files: nothing behind the level-K subbands of a file is decoded.  The size must offer the level
+(both sides multiples of 2^(K+1)); it composes with --temporal-level, --motion-fill, --png and --output-layout.  Level 1 and
+above are checked against spatial_hashes.json (tools/encode_sequence.py --spatial-hashes).  A folder with a display form of
+its own is decoded this way only with --coded-size-output (and --coded-format-output where the source was not 4:2:0).
 --output-layout NAME (pmctf_layout) writes every picture in that pixel layout (nv12, p010, v210, ...), packed
 on the GPU after the steps above; the layout must have the chroma format and depth of the pictures being written."""
 import argparse
@@ -53,6 +58,8 @@ def main(argv=None):
                     help="decode at 1/2^K of the frame rate from the files of that level alone (default: everything)")
     ap.add_argument("--motion-fill", action="store_true",
                     help="with --temporal-level: full frame rate, the left-out high bands taken as zero (never verified)")
+    ap.add_argument("--spatial-level", type=int, metavar="K",
+                    help="decode at 1/2^K of the picture size from the coarse subbands alone (default: the full size)")
     ap.add_argument("--coded-size-output", action="store_true",
                     help="a folder coded with --coded-size: write the coded-size pictures, not the display-size ones")
     ap.add_argument("--coded-format-output", action="store_true",
@@ -64,6 +71,8 @@ def main(argv=None):
     layered = a.temporal_level is not None or a.motion_fill
     if layered and (a.temporal_level or 0) < 0:
         ap.error("--temporal-level is 0 or more")
+    if a.spatial_level is not None and not 0 <= a.spatial_level <= 4:
+        ap.error("--spatial-level is 0 to 4")
     if a.motion_fill and a.verify is True:
         ap.error("--motion-fill output has no hashes: it cannot be combined with --verify")
     if a.yuv_out is None and a.png is None:
@@ -80,7 +89,15 @@ def main(argv=None):
     import pmctf_gop
     from pMCTF.models.video.pMCTF_L import pMCTF
     header, _ = pmctf_gop.sequence_layout(a.bin_folder)
-    net = pMCTF(num_me_stages=header["num_me_stages"]).eval()
+    if a.spatial_level:                                  # what needs no weights is refused before they are loaded
+        import pmctf_layers
+        try:
+            mode = pmctf_layers.LayerDecode(a.temporal_level or 0, a.motion_fill, a.spatial_level)
+            mode.refuse(a.verify)
+            mode.picture_size(a.bin_folder, header["height"], header["width"], a.coded_size_output, a.coded_format_output)
+        except ValueError as e:
+            ap.error(f"--spatial-level: {e}")
+    net =pMCTF(num_me_stages=header["num_me_stages"]).eval()
     if a.checkpoint is not None:
         from pMCTF.utils.stream_helper import get_state_dict
         net.load_state_dict(get_state_dict(a.checkpoint), strict=True)
@@ -91,7 +108,14 @@ def main(argv=None):
     net.update(force=True)
     with torch.no_grad():
         try:
-            if layered:
+            if a.spatial_level is not None:
+                import pmctf_spatial
+                out = pmctf_spatial.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
+                                                          png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
+                                                          coded_size_output=a.coded_size_output,
+                                                          coded_format_output=a.coded_format_output,
+                                                          output_layout=a.output_layout, spatial_level=a.spatial_level)
+            elif layered:
                 out = pmctf_layout.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
                                                          png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
                                                          coded_size_output=a.coded_size_output,
@@ -115,7 +139,10 @@ def main(argv=None):
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
                       "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"]),
                       **({"temporal_level": out["level"], "motion_fill": a.motion_fill, "bytes_read": out["bytes_read"]}
-                         if layered else {})}))
+                         if layered or a.spatial_level is not None else {}),
+                      **({"spatial_level": out["spatial_level"],
+                          "payload_bytes_used": sum(sum(g.values()) for g in out["payload_bytes_used"])}
+                         if a.spatial_level is not None else {})}))
     for m in out["hash_mismatches"]:
         print(pmctf_gop.describe_hash_mismatch(m), file=sys.stderr)
     if out["hash_mismatches"]:

@@ -20,6 +20,9 @@ gop_structure.json instead of sequence.json, which tools/decode_sequence.py read
 --layer-hashes: after the encode the folder is decoded once more (pmctf_layers.write_layer_hashes, checked against the
 picture hashes where there are any) and BIN_FOLDER/layer_hashes.json records the CRC-32 of every picture of every temporal
 layer, which tools/decode_sequence.py --temporal-level K checks.
+--spatial-hashes: the same for the spatial layers (pmctf_spatial.write_spatial_hashes): BIN_FOLDER/spatial_hashes.json
+records every picture of every (spatial level, temporal level) the picture size offers, which tools/decode_sequence.py
+--spatial-level K checks.
 --bitrate BITS_PER_S --fps N[/D] (pmctf_rate.encode_sequence_rate): instead of one --q-index for the sequence every GOP gets
 its own, chosen from --q-min..--q-max by coding the GOP up to --max-trials times so that the sequence keeps to the bitrate
 (--bucket-ms: how much unspent rate is carried on; --slack: stop raising q_index within that fraction of the budget;
@@ -87,6 +90,8 @@ def main(argv=None):
                     help="chroma format of a raw planar source (default 420; a .y4m says its own)")
     ap.add_argument("--layer-hashes", action="store_true",
                     help="also record the hashes of the temporal layers (layer_hashes.json), from a full decode of the folder")
+    ap.add_argument("--spatial-hashes", action="store_true",
+                    help="also record the hashes of the spatial layers (spatial_hashes.json), from reduced decodes of the folder")
     ap.add_argument("--coded-size", metavar="WxH", help="code at this size instead of the source's (even, within a factor of 4)")
     ap.add_argument("--chroma-loc", choices=("center", "left"),
                     help="--coded-size: where the source's chroma samples lie (center: the default; left: MPEG-2 siting)")
@@ -265,6 +270,13 @@ def main(argv=None):
             except pmctf_gop.PictureHashMismatch as e:
                 sys.exit(f"picture hash mismatch, no layer hashes written: {e}")
             print(f"layer hashes: {path}", file=sys.stderr)
+        if a.spatial_hashes:
+            import pmctf_spatial
+            try:
+                path = pmctf_spatial.write_spatial_hashes(net, a.bin_folder)
+            except pmctf_gop.PictureHashMismatch as e:
+                sys.exit(f"picture hash mismatch, no spatial hashes written: {e}")
+            print(f"spatial hashes: {path}", file=sys.stderr)
     if out.get("display_quality"):
         mean = {k: sum(q[k] for q in out["display_quality"]) / len(out["display_quality"]) for k in out["display_quality"][0]}
         print(f"coded at {coded_size[0]}x{coded_size[1]}; at {width}x{height} against the source: " +
