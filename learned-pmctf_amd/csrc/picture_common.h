@@ -1,6 +1,6 @@
 // What the picture kernels share besides the colour arithmetic (picture_math.h): the launch shape and the size limits
-// of picture_ops.hip, picture_hbd.hip, picture_scale.hip, picture_chroma.hip, picture_layout.hip, quality_ops.hip and
-// scene_ops.hip, the
+// of picture_ops.hip, picture_hbd.hip, picture_scale.hip, picture_chroma.hip, picture_layout.hip, quality_ops.hip,
+// quality_planar.hip and scene_ops.hip, the
 // workgroup sum, and the access to four neighbouring samples of either width (uint8_t at bit depth 8, uint16_t at 9..16).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -17,8 +17,8 @@ and the entry points encode_sequence, encode_sequence_gops, encode_sequence_rate
 decode_sequence_layer: pmctf_scale's functions with the keywords chroma_format (encoding) and coded_format_output
 (decoding) added.  With a raw 4:2:0 source and chroma_format=None they do what pmctf_scale's functions do.
 
-Out of scope: 4:0:0, 420paldv, 4:1:1, alpha, interlaced material; quality figures in the source's own format (the tables
-are those of the coded 4:2:0 pictures against the converted source)."""
+Out of scope: 4:0:0, 420paldv, 4:1:1, alpha, interlaced material.  The encoders' quality tables are those of the coded
+4:2:0 pictures against the converted source; figures in the source's own format come from pmctf_quality."""
 import functools
 import os
 import re

@@ -31,7 +31,11 @@ coarse subbands of the same files: nothing behind the level-K subbands of a file
 above are checked against spatial_hashes.json (tools/encode_sequence.py --spatial-hashes).  A folder with a display form of
 its own is decoded this way only with --coded-size-output (and --coded-format-output where the source was not 4:2:0).
 --output-layout NAME (pmctf_layout) writes every picture in that pixel layout (nv12, p010, v210, ...), packed
-on the GPU after the steps above; the layout must have the chroma format and depth of the pictures being written."""
+on the GPU after the steps above; the layout must have the chroma format and depth of the pictures being written.
+--compare SOURCE (pmctf_quality.compare_files) compares the file just written with SOURCE, in the chroma format
+and at the bit depth both have: one line per frame and the averages, per-plane PSNR and MS-SSIM.  SOURCE is a .y4m, or a raw
+planar file of the size, chroma format and depth of what was written; it needs an OUT file and is refused together with
+--output-layout, --spatial-level and --temporal-level, whose outputs are not pictures of the source's form."""
 import argparse
 import json
 import os
@@ -65,6 +69,8 @@ def main(argv=None):
     ap.add_argument("--coded-format-output", action="store_true",
                     help="a folder with a source_format.json: write the coded 4:2:0 pictures, not the source's chroma format")
     ap.add_argument("--output-layout", metavar="NAME", help="write the pictures in this pixel layout (pmctf_layout.LAYOUTS)")
+    ap.add_argument("--compare", metavar="SOURCE",
+                    help="after the decode, compare OUT with this file: per-plane PSNR and MS-SSIM in their own format")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args(argv)
@@ -77,6 +83,15 @@ def main(argv=None):
         ap.error("--motion-fill output has no hashes: it cannot be combined with --verify")
     if a.yuv_out is None and a.png is None:
         ap.error("give OUT.yuv, --png DIR or both")
+    if a.compare is not None:
+        if a.yuv_out is None:
+            ap.error("--compare: needs an OUT file to compare with")
+        for flag, given in (("--output-layout", a.output_layout), ("--spatial-level", a.spatial_level),
+                            ("--temporal-level", a.temporal_level)):
+            if given is not None:
+                ap.error(f"--compare: cannot be combined with {flag} (its output is not a picture of the source's form)")
+        if not os.path.exists(a.compare):
+            ap.error(f"--compare: no such file: {a.compare}")
     import pmctf_layout
     if a.output_layout is not None:
         try:
@@ -147,6 +162,17 @@ def main(argv=None):
         print(pmctf_gop.describe_hash_mismatch(m), file=sys.stderr)
     if out["hash_mismatches"]:
         sys.exit(1)
+    if a.compare is not None:
+        import pmctf_chroma
+        import pmctf_quality
+        record = None if a.coded_format_output else pmctf_chroma.read_source_format(a.bin_folder)
+        try:                                             # a raw file has the form of what was written; a .y4m its own
+            q = pmctf_quality.compare_files(a.compare, a.yuv_out, a.device, width=width, height=height,
+                                            chroma_format="420" if record is None else record["chroma_format"],
+                                            bitdepth=out["bitdepth"])
+        except ValueError as e:
+            sys.exit(f"--compare: {e}")
+        pmctf_quality.print_report(q)
 
 
 if __name__ == "__main__":

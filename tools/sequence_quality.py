@@ -6,7 +6,7 @@
 One line per frame in the evaluation script's wording, then the averages.  With tools/decode_sequence.py this closes the
 loop  bitstream folder -> .yuv -> quality.  The metrics run on the GPU (pmctf_gop.sequence_quality).  --bitdepth B (9..16):
 both files hold little-endian 16-bit samples of that depth; the PSNRs are against 2^B - 1, RGB-PSNR and MS-SSIM (defined
-on 8-bit RGB) are reported as 0."""
+on 8-bit RGB) are reported as 0.  Per-plane MS-SSIM at the files' own depth and chroma format: tools/compare_sequences.py."""
 import argparse
 import json
 import os
