@@ -489,12 +489,19 @@ class HipEngine:
         L_t = ew(EW_ADD, ref, inv)
         return L_t, H_t, pred, inv
 
-    def inverse_MCTF(self, L_t, H_t, mv_hat, downscale=False, stage_idx=0):
+    def inverse_MCTF_ref(self, L_t, H_t, mv_hat, downscale=False, stage_idx=0):
+        """the first half of inverse_MCTF: `ref` alone, for a pair whose `cur` nobody asks for (pmctf_access)"""
         me = min(self.num_me_stages - 1, stage_idx)
         if downscale:
             mv_hat = ops.bilinear_down2(mv_hat, 2.0)
         inv = self.update_filter(me, self.warp(H_t, mv_hat, -1.0))
-        ref = ew(EW_SUB, L_t, inv)
+        return ew(EW_SUB, L_t, inv)
+
+    def inverse_MCTF(self, L_t, H_t, mv_hat, downscale=False, stage_idx=0):
+        me = min(self.num_me_stages - 1, stage_idx)
+        if downscale:
+            mv_hat = ops.bilinear_down2(mv_hat, 2.0)
+        ref = self.inverse_MCTF_ref(L_t, H_t, mv_hat, stage_idx=stage_idx)
         pred = self.predict_filter(me, self.warp(ref, mv_hat))
         cur = ew(EW_ADD, H_t, pred)
         return ref, cur

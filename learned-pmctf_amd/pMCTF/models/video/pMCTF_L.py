@@ -290,6 +290,14 @@ class pMCTF(nn.Module):
 
     @torch.no_grad()
     @_gated
+    def inverse_MCTF_ref(self, L_t, H_t, mv_hat, downscale=False, stage_idx=0):
+        """inverse_MCTF(...)[0] without the predict half: the same tensor, bit for bit"""
+        L_t, H_t, mv_hat = unwrap((L_t, H_t, mv_hat))
+        c = lambda t: t.contiguous()
+        return self.engine().inverse_MCTF_ref(c(L_t), c(H_t), c(mv_hat), downscale=downscale, stage_idx=stage_idx)
+
+    @torch.no_grad()
+    @_gated
     def forward_MCTF(self, ref_frame, cur_frame, mv_hat, stage_idx=0):
         """pMCTF_L.py:297-312"""
         ref_frame, cur_frame, mv_hat = unwrap((ref_frame, cur_frame, mv_hat))

@@ -1180,6 +1180,7 @@ class FullDecode:
     how one GOP is decoded and which recorded hashes apply to its pictures.  pmctf_layers.LayerDecode is the one for a
     temporal level."""
     hash_level = None                                                     # None: nothing to check the pictures against
+    keeps = False                                                         # True: `taken` is the output, nothing need be written
 
     def refuse(self, verify):
         """refusals of its own, raised between that of `verify` and that of having nothing to write"""
@@ -1198,13 +1199,17 @@ class FullDecode:
             self.frames, self.hash_level = full["frames"], full["level"]
 
     def decode_gop(self, codec, folder, size, h, w, q_index, psize, me_downsample, ll_order):
-        """-> (the GOP's pictures, their offsets within the GOP, the bytes read or None where they are not counted)"""
+        """-> (the GOP's pictures, their offsets within the GOP, the bytes read or None where they are not counted); no
+        pictures and no offsets for a GOP the mode leaves out (pmctf_access.FrameDecode), whose folder is then not touched"""
         out = decode_gop_files(codec, folder, size, h, w, q_index, psize=psize, me_downsample=me_downsample, ll_order=ll_order)
         return out["frames"], range(size), None
 
     def recorded(self, first, size, at, n):
         """-> the records of the n pictures decoded from the GOP of `size` pictures at `first`, `at` pictures written so far"""
         return self.frames[first:first + size]
+
+    def taken(self, source, frames, bitdepth):
+        """every GOP's pictures (padded, on the device) with their source indices, once verified and before they are written"""
 
     def result(self, times, nbytes):
         return {}
@@ -1215,13 +1220,14 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
     """The one sequence decoder: decode_sequence_checked (mode: a FullDecode) and pmctf_layers.decode_sequence_layer (a
     LayerDecode), and under the output flags pmctf_scale's and pmctf_chroma's forms of both; with an output_layout
     (pmctf_layout) the pictures of the sink are packed on the device before they are written.  A FullDecode and a LayerDecode
-    of level 0 without motion_fill decode the same pictures in the same order, so they write the same bytes."""
+    of level 0 without motion_fill decode the same pictures in the same order, so they write the same bytes.  A
+    pmctf_access.FrameDecode decodes chosen pictures: a GOP for which the mode returns no pictures is passed over."""
     import contextlib
     import time
     if not any(verify is v for v in (True, False)) and verify not in ("auto", "report"):
         raise ValueError(f"verify is 'auto', True, False or 'report' (got {verify!r})")
     mode.refuse(verify)
-    if yuv_out is None and png_out is None:
+    if yuv_out is None and png_out is None and not mode.keeps:
         raise ValueError("nothing to write: give yuv_out, png_out or both")
     header, gops = sequence_layout(bin_folder)
     mode.check_folder(bin_folder)
@@ -1256,6 +1262,9 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
             frames, offsets, nread = mode.decode_gop(codec, folder, size, h, w, q_indexes[k], psize, me_downsample,
                                                      header["ll_order"])
             source = [first + t for t in offsets]                         # the source index of every decoded picture
+            if not source:                                                # a GOP the mode left out
+                seconds.append(time.time() - t0)
+                continue
             if mode.hash_level is not None:
                 got = picture_hashes(frames, ph, pw, mode.hash_level, bitdepth)
                 bad = []
@@ -1265,6 +1274,7 @@ def decode_sequence_with(mode, codec, bin_folder, yuv_out, device=None, png_out=
                     raise PictureHashMismatch(bad[0])
                 mismatches += bad
                 verified += len(source)
+            mode.taken(source, frames, bitdepth)
             if f is not None:
                 for planes in sink.pictures(frames):
                     f.write(sink.frame_marker)

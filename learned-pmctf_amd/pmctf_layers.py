@@ -97,6 +97,17 @@ def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psiz
     those of pmctf_gop.decode_gop_files.  spatial_level=k: the planes of every picture file at spatial level k (the
     motion fields stay as coded: reduce_motion).  counters: a dict that receives, per picture file name, what the engine
     says it read of it: {"symbols_decoded", "payload_bytes_used"}."""
+    pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
+    return _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order,
+                           {i_cur for stage, _, i_cur in pairs if stage >= kk},
+                           {i_cur for stage, _, i_cur in pairs if stage >= kk or motion_fill}, spatial_level, counters)
+
+
+def _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, pictures,
+                    motions, spatial_level=0, counters=None):
+    """the reader of _read_gop_layer and of pmctf_access: of the pairs of the GOP, in coding order, the two picture files of
+    those whose i_cur is in `pictures` and the motion file of those whose i_cur is in `motions`, then the two L files.
+    `motions` holds, of every stage it touches, the pairs from the stage's first on: the context runs pair to pair."""
     import struct
     import torch
     pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
@@ -121,12 +132,12 @@ def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psiz
 
     motion = []
     for stage, _, i_cur in pairs:
-        if stage < kk and not motion_fill:
-            continue
         me_num = min(codec.num_me_stages - 1, stage)
-        if stage >= kk:
+        if i_cur in pictures:
             picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
             picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
+        if i_cur not in motions:
+            continue
         path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
         data = pmctf_gop._read_framed(path, 6)
         motion.append((stage, i_cur, me_num, path, data[6:]))

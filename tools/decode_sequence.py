@@ -35,7 +35,13 @@ on the GPU after the steps above; the layout must have the chroma format and dep
 --compare SOURCE (pmctf_quality.compare_files) compares the file just written with SOURCE, in the chroma format
 and at the bit depth both have: one line per frame and the averages, per-plane PSNR and MS-SSIM.  SOURCE is a .y4m, or a raw
 planar file of the size, chroma format and depth of what was written; it needs an OUT file and is refused together with
---output-layout, --spatial-level and --temporal-level, whose outputs are not pictures of the source's form."""
+--output-layout, --spatial-level and --temporal-level, whose outputs are not pictures of the source's form.
+--frames SPEC (pmctf_access.decode_frames) decodes chosen pictures alone: SPEC is N, A:B (half-open, as in Python)
+or a comma list of those, e.g. 37 or 1000:1100 or 0,8:12,40.  Only the GOPs that hold one of them are opened, and of those
+only the files the pictures depend on; the pictures are written in ascending order, the PNGs under their source indices, and
+each is checked against its own picture hash.  It composes with --png, --spatial-level, --coded-size-output,
+--coded-format-output, --output-layout and the verify flags, and is refused together with --temporal-level, --motion-fill
+and --compare.  The summary then holds the bytes of the files read and the number of GOPs opened."""
 import argparse
 import json
 import os
@@ -43,6 +49,20 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "learned-pmctf_amd"))
+
+
+def parse_frames(spec):
+    """--frames SPEC -> the picture indices it names, in the order given; ValueError naming the malformed part"""
+    out = []
+    for part in spec.split(","):
+        ends = part.split(":")
+        if len(ends) > 2 or not all(e.strip().isdigit() for e in ends):
+            raise ValueError(f"{part!r} is neither N nor A:B")
+        ends = [int(e) for e in ends]
+        out += list(range(*ends)) if len(ends) == 2 else ends
+        if len(ends) == 2 and ends[0] >= ends[1]:
+            raise ValueError(f"{part!r} selects no picture")
+    return out
 
 
 def main(argv=None):
@@ -71,6 +91,8 @@ def main(argv=None):
     ap.add_argument("--output-layout", metavar="NAME", help="write the pictures in this pixel layout (pmctf_layout.LAYOUTS)")
     ap.add_argument("--compare", metavar="SOURCE",
                     help="after the decode, compare OUT with this file: per-plane PSNR and MS-SSIM in their own format")
+    ap.add_argument("--frames", metavar="SPEC",
+                    help="decode these pictures alone, from the files they depend on: N, A:B (half-open) or a comma list")
     ap.add_argument("bin_folder")
     ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
     a = ap.parse_args(argv)
@@ -92,6 +114,16 @@ def main(argv=None):
                 ap.error(f"--compare: cannot be combined with {flag} (its output is not a picture of the source's form)")
         if not os.path.exists(a.compare):
             ap.error(f"--compare: no such file: {a.compare}")
+    frames = None
+    if a.frames is not None:
+        for flag, given in (("--temporal-level", a.temporal_level is not None), ("--motion-fill", a.motion_fill),
+                            ("--compare", a.compare is not None)):
+            if given:
+                ap.error(f"--frames: cannot be combined with {flag}")
+        try:
+            frames = parse_frames(a.frames)
+        except ValueError as e:
+            ap.error(f"--frames: {e}")
     import pmctf_layout
     if a.output_layout is not None:
         try:
@@ -112,6 +144,12 @@ def main(argv=None):
             mode.picture_size(a.bin_folder, header["height"], header["width"], a.coded_size_output, a.coded_format_output)
         except ValueError as e:
             ap.error(f"--spatial-level: {e}")
+    if frames is not None:
+        import pmctf_access
+        try:
+            pmctf_access.FrameDecode(frames, a.spatial_level or 0).check_folder(a.bin_folder)
+        except ValueError as e:
+            ap.error(f"--frames: {e}")
     net =pMCTF(num_me_stages=header["num_me_stages"]).eval()
     if a.checkpoint is not None:
         from pMCTF.utils.stream_helper import get_state_dict
@@ -123,7 +161,12 @@ def main(argv=None):
     net.update(force=True)
     with torch.no_grad():
         try:
-            if a.spatial_level is not None:
+            if frames is not None:
+                out = pmctf_access.decode_frames(net, a.bin_folder, a.yuv_out, frames, a.device, png_out=a.png,
+                                                 verify=a.verify, spatial_level=a.spatial_level or 0,
+                                                 coded_size_output=a.coded_size_output,
+                                                 coded_format_output=a.coded_format_output, output_layout=a.output_layout)
+            elif a.spatial_level is not None:
                 import pmctf_spatial
                 out = pmctf_spatial.decode_sequence_layer(net, a.bin_folder, a.yuv_out, a.temporal_level or 0, a.device,
                                                           png_out=a.png, verify=a.verify, motion_fill=a.motion_fill,
@@ -153,11 +196,13 @@ def main(argv=None):
                       "bitdepth": out["bitdepth"],
                       "seconds": sum(out["seconds"]), "frames_per_second": n / max(sum(out["seconds"]), 1e-9),
                       "verified": out["verified"], "hash_mismatches": len(out["hash_mismatches"]),
+                      **({"frames_wanted": out["times"], "bytes_read": out["bytes_read"], "gops_opened": out["gops_opened"],
+                          "spatial_level": out["spatial_level"]} if frames is not None else {}),
                       **({"temporal_level": out["level"], "motion_fill": a.motion_fill, "bytes_read": out["bytes_read"]}
-                         if layered or a.spatial_level is not None else {}),
+                         if frames is None and (layered or a.spatial_level is not None) else {}),
                       **({"spatial_level": out["spatial_level"],
                           "payload_bytes_used": sum(sum(g.values()) for g in out["payload_bytes_used"])}
-                         if a.spatial_level is not None else {})}))
+                         if frames is None and a.spatial_level is not None else {})}))
     for m in out["hash_mismatches"]:
         print(pmctf_gop.describe_hash_mismatch(m), file=sys.stderr)
     if out["hash_mismatches"]:
