@@ -8,7 +8,7 @@ the motion files chain, pair to pair within a stage and restarting at every stag
 of a stage needs the motion files of the pairs 0..g of that stage and nothing of another stage.  Of a pair whose `cur`
 side nobody needs only the update half of the lifting runs (inverse_MCTF_ref).
   check_frames, gop_plan, access_plan, access_file_names, access_bytes   the plan (pure Python)
-  decode_gop_files_frames, decode_frames, read_frames                    the decoder, on pmctf_layers' reader and batch
+  decode_gop_files_frames, decode_frames, read_frames                    the decoder, on pmctf_layers' per-GOP body
 The worked example, a GOP of 8 and picture 5:
   needed = {0: [5], 1: [4], 2: [4], 3: [0]}        pairs = [(2, 0, 4, True), (1, 4, 6, False), (0, 4, 5, True)]
   files  = 1_mv 3_mv 5 5_C_main 5_mv | 2_mv 6 6_C_main 6_mv | 4 4_C_main 4_mv | 0_main 0_C_main: 14 of the GOP's 23 files,
@@ -103,15 +103,8 @@ def access_bytes(bin_folder, frames):
     """the sizes of exactly the files a decode of `frames` from the sequence in bin_folder reads, summed over the GOPs that
     hold one of them: pmctf_layers.layer_bytes' counterpart.  ValueError naming a file that is missing."""
     header, gops = pmctf_gop.sequence_layout(bin_folder)
-    total = 0
-    for k, local in access_plan(gops, check_frames(frames, header["frame_num"])):
-        for name in access_file_names(gops[k][1], local):
-            path = os.path.join(bin_folder, pmctf_gop.gop_folder(k), name)
-            try:
-                total += os.path.getsize(path)
-            except FileNotFoundError:
-                raise ValueError(f"{path}: missing") from None
-    return total
+    return pmctf_layers.files_bytes(bin_folder, ((k, access_file_names(gops[k][1], local))
+                                                 for k, local in access_plan(gops, check_frames(frames, header["frame_num"]))))
 
 
 # ---------------------------------------------------------------------------------------------------------------- one GOP
@@ -128,41 +121,15 @@ def decode_gop_files_frames(codec, bin_folder, gop, pic_height, pic_width, q_ind
     Returns {"frames": [[Y, UV, None]] (padded) in the order of `wanted`, "times": wanted, "files": the names read, in
     order, "bytes_read", "stages", "pairs": the plan's, "half_pairs": how many ran `ref` alone, "spatial_level", "size":
     (height, width) of the pictures, "symbols_decoded" and "payload_bytes_used" as decode_gop_files_layer reports them}."""
-    import torch
-    pmctf_layers._check_decode_args(0, False, ll_order, spatial_level)
-    if not any(one_sided is v for v in (True, False)):
-        raise ValueError(f"one_sided is True or False (got {one_sided!r})")
-    size = pmctf_spatial.spatial_size(pic_height, pic_width, spatial_level)
-    plan = gop_plan(gop, wanted)
-    pictures = {i_cur for _, _, i_cur, _ in plan["pairs"]}
-    motions = {int(n.split("_")[0]) for n in plan["motion_files"]}
-    counters = {}
-    half = 0
-    with torch.no_grad():
-        coded, read, nbytes = pmctf_layers._read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize,
-                                                           me_downsample, ll_order, pictures, motions, spatial_level, counters)
-        for i in motions - pictures:                      # decoded for the context of a later pair alone
-            coded[i][2] = None
-        pmctf_layers.reduce_motion(coded, spatial_level)
-        for stage, i_ref, i_cur, want_cur in plan["pairs"]:
-            me_num = min(codec.num_me_stages - 1, stage)
-            L_t, L_tc, mv_ref = coded[i_ref]
-            H_t, H_tc, mv_hat = coded[i_cur]
-            assert mv_ref is None
-            if want_cur or not one_sided:
-                ref, cur = codec.inverse_MCTF(L_t, H_t, mv_hat, stage_idx=me_num)
-                ref_c, cur_c = codec.inverse_MCTF(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
-                coded[i_cur] = [cur, cur_c, None]
-            else:
-                ref = codec.inverse_MCTF_ref(L_t, H_t, mv_hat, stage_idx=me_num)
-                ref_c = codec.inverse_MCTF_ref(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
-                half += 1
-            coded[i_ref] = [ref, ref_c, None]
-    return {"frames": [coded[t] for t in plan["needed"][0]], "times": list(plan["needed"][0]), "files": read,
-            "bytes_read": nbytes, "stages": pmctf_layers.gop_stages(gop), "pairs": plan["pairs"], "half_pairs": half,
-            "spatial_level": spatial_level, "size": size,
-            "symbols_decoded": {n: c["symbols_decoded"] for n, c in counters.items()},
-            "payload_bytes_used": {n: c["payload_bytes_used"] for n, c in counters.items()}}
+    def plan():
+        found = gop_plan(gop, wanted)
+        return (found["pairs"], {i_cur for _, _, i_cur, _ in found["pairs"]},
+                {int(n.split("_")[0]) for n in found["motion_files"]}, [], list(found["needed"][0]))
+
+    out, pairs = pmctf_layers._decode_gop_planned(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample,
+                                                  ll_order, spatial_level, plan, one_sided=one_sided)
+    del out["frames_coded"]
+    return dict(out, pairs=pairs, half_pairs=sum(not want_cur for _, _, _, want_cur in pairs) if one_sided else 0)
 
 
 # ------------------------------------------------------------------------------------------------------------ a sequence
@@ -176,12 +143,12 @@ class FrameDecode(pmctf_gop.FullDecode):
     "gops_opened", "half_pairs", "spatial_level" and "size"."""
 
     def __init__(self, frames, spatial_level=0, one_sided=True, keep=False):
-        self.layer = pmctf_layers.LayerDecode(0, False, spatial_level)    # its checks of a spatial level are the ones here
+        pmctf_layers._check_decode_args(0, False, spatial_level=spatial_level)
         self.frames_given, self.spatial_level, self.one_sided, self.keeps = frames, spatial_level, one_sided, keep
-        self.size, self.kept, self.opened, self.half_pairs = None, [], 0, 0
+        self.verify, self.size, self.kept, self.opened, self.half_pairs = "auto", None, [], 0, 0
 
     def refuse(self, verify):
-        self.layer.refuse(verify)
+        self.verify = verify
 
     def check_folder(self, bin_folder):
         marker = pmctf_layers.read_layer_extract(bin_folder)
@@ -194,7 +161,8 @@ class FrameDecode(pmctf_gop.FullDecode):
         self.by_first = {gops[k][0]: local for k, local in plan}
 
     def picture_size(self, bin_folder, h, w, coded_size_output, coded_format_output):
-        self.size = self.layer.picture_size(bin_folder, h, w, coded_size_output, coded_format_output)
+        self.size = pmctf_layers.spatial_picture_size(bin_folder, h, w, self.spatial_level, self.verify, coded_size_output,
+                                                      coded_format_output)
         return self.size
 
     def open(self, bin_folder, header, gops, verify):

@@ -181,23 +181,47 @@ def decode_gop(codec, frames_coded, luma_stage0=False):
     """Temporal synthesis, test_pMCTF_flex.py:268-291.  Modifies and returns frames_coded.
     luma_stage0: the content-adaptive harness's variant, which reconstructs luma with stage 0's lifting filters at every
     stage (inverse_MCTF without stage_idx, test_pMCTF_CA.py:239)."""
-    gop = len(frames_coded)
+    return synthesise(codec, frames_coded, synthesis_pairs(len(frames_coded)), luma_stage0=luma_stage0)
+
+
+def synthesis_pairs(gop, down_to=0):
+    """[(stage, i_ref, i_cur, True)] in synthesis order: every pair of the stages S-1 .. down_to of a GOP of 2^S pictures,
+    each stage from its last group to its first.  The True is want_cur (synthesise): both sides of every pair."""
     stages = int(round(math.log2(gop)))
-    num_frames = 1
-    for stage_idx in reversed(range(stages)):
-        if stage_idx != stages - 1:
-            num_frames *= 2
-        for group_idx in reversed(range(num_frames)):
-            step = 2 ** stage_idx
-            i_ref = group_idx * 2 * step
-            L_t, L_tc, mv_ref = frames_coded[i_ref]
-            H_t, H_tc, mv_hat = frames_coded[i_ref + step]
-            assert mv_ref is None
-            me_num = min(codec.num_me_stages - 1, stage_idx)
-            ref, cur = codec.inverse_MCTF(L_t, H_t, mv_hat, stage_idx=0 if luma_stage0 else me_num)
+    return [(s, g << (s + 1), (g << (s + 1)) + (1 << s), True)
+            for s in reversed(range(down_to, stages)) for g in reversed(range(gop >> (s + 1)))]
+
+
+def synthesise(codec, frames_coded, pairs, luma_stage0=False, one_sided=False, snapshots=None):
+    """The one temporal synthesis loop (test_pMCTF_flex.py:268-291): the pairs (stage, i_ref, i_cur, want_cur) in the order
+    given, luma and then chroma (downscale=True) of each through codec.inverse_MCTF, [ref, ref_c, None] and [cur, cur_c,
+    None] written back.  Modifies and returns frames_coded.
+    one_sided: of a pair whose want_cur is False only `ref` is computed (codec.inverse_MCTF_ref: the same tensor without the
+    predict half) and the `cur` entry stays as it is.  synthesis_pairs never asks for that, so a codec without that method
+    (the oracle model, the reference network) serves decode_gop.
+    snapshots: a dict that receives, per level k, the low-band entries ([Y, UV, None] at the indices j * 2^k) as the list
+    holds them once stage k is undone, and under S the state before the first pair; for pairs of synthesis_pairs."""
+    def keep(k):
+        if snapshots is not None:
+            snapshots[k] = [list(frames_coded[j << k]) for j in range(len(frames_coded) >> k)]
+
+    keep(int(round(math.log2(len(frames_coded)))))
+    for n, (stage, i_ref, i_cur, want_cur) in enumerate(pairs):
+        L_t, L_tc, mv_ref = frames_coded[i_ref]
+        H_t, H_tc, mv_hat = frames_coded[i_cur]
+        assert mv_ref is None
+        me_num = min(codec.num_me_stages - 1, stage)
+        me_luma = 0 if luma_stage0 else me_num
+        if want_cur or not one_sided:
+            ref, cur = codec.inverse_MCTF(L_t, H_t, mv_hat, stage_idx=me_luma)
             ref_c, cur_c = codec.inverse_MCTF(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
-            frames_coded[i_ref] = [ref, ref_c, None]
-            frames_coded[i_ref + step] = [cur, cur_c, None]
+            frames_coded[i_cur] = [cur, cur_c, None]
+        else:
+            ref = codec.inverse_MCTF_ref(L_t, H_t, mv_hat, stage_idx=me_luma)
+            ref_c = codec.inverse_MCTF_ref(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
+        frames_coded[i_ref] = [ref, ref_c, None]
+        if n + 1 == len(pairs) or pairs[n + 1][0] != stage:
+            keep(stage)
     return frames_coded
 
 
@@ -825,6 +849,81 @@ def _read_framed(path, header_bytes):
     return data
 
 
+def _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, pictures=None,
+                    motions=None, spatial_level=0, counters=None):
+    """The one reader of a GOP's files, under every decoder: of the pairs of the GOP, in coding order, the two picture files
+    of those whose i_cur is in `pictures` and the motion file of those whose i_cur is in `motions` (None: of every pair),
+    then the two L files; gop == 1: the two L files alone.  `motions` holds, of every stage it touches, the pairs from the
+    stage's first on: the context runs pair to pair.  Every file is read and its header checked before the codec is touched.
+    The picture files are started as ONE batch (codec._decompress_gop_files_begin), under it the motion files are decoded in
+    coding order (the context restarts per stage, as in encode_gop: what makes the temporal layers independent; a
+    reduced-resolution stream is decoded at the size it was coded at), then the batch is finished.
+    spatial_level=k: the planes of every picture file at spatial level k (the motion fields stay as coded).  counters: a
+    dict that receives, per picture file name, what the engine says it read of it: {"symbols_decoded",
+    "payload_bytes_used"}.
+    -> (frames_coded: [L_t / H_t, L_tc / H_tc, mv_hat] entries with None where nothing was read, names read, bytes read)."""
+    import struct
+    pairs = gop_pairs(gop) if gop != 1 else []          # a lone picture (pmctf_seq): its two L files, no motion
+    pad_h = -(-pic_height // psize) * psize
+    pad_w = -(-pic_width // psize) * psize
+    files, paths, slots, read = [], [], [], []
+    nbytes = 0
+
+    def picture(name, chroma, low, me_num, slot):
+        nonlocal nbytes
+        path = os.path.join(bin_folder, name)
+        data = _read_framed(path, 16)
+        h, w, n = struct.unpack(">III", data[:12])
+        want = (pic_height // 2, pic_width // 2, 2) if chroma else (pic_height, pic_width, 1)
+        if (h, w, n) != want:
+            raise ValueError(f"{path}: header says {n} plane(s) of {h}x{w}, expected {want[2]} of {want[0]}x{want[1]}")
+        files.append((data, chroma, low, me_num))
+        paths.append(path)
+        slots.append(slot)
+        read.append(name)
+        nbytes += len(data)
+
+    motion = []
+    for stage, _, i_cur in pairs:
+        me_num = min(codec.num_me_stages - 1, stage)
+        if pictures is None or i_cur in pictures:
+            picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
+            picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
+        if motions is not None and i_cur not in motions:
+            continue
+        path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
+        data = _read_framed(path, 6)
+        motion.append((stage, i_cur, me_num, path, data[6:]))
+        read.append(f"{i_cur}_mv.bin")
+        nbytes += len(data)
+    picture("0_main.bin", False, True, 0, (0, 0))
+    picture("0_C_main.bin", True, True, 0, (0, 1))
+
+    begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, paths, spatial_level=spatial_level)
+    frames_coded = [[None, None, None] for _ in range(gop)]
+    dpb, at_stage = None, None
+    try:
+        for stage, i_cur, me_num, path, string in motion:
+            if stage != at_stage:
+                dpb, at_stage = {"mv_feature": None, "ref_mv_y": None}, stage
+            try:
+                d = codec.decompress_mv(string, torch.float32, pad_h // me_downsample, pad_w // me_downsample, dpb,
+                                        stage_idx=me_num, q_index=q_index, me_downsample=me_downsample)
+            except (ValueError, RuntimeError) as e:
+                raise ValueError(f"{path}: {e}") from e
+            frames_coded[i_cur][2] = d["mv_hat"]
+            dpb = {"mv_feature": d["mv_feature"], "ref_mv_y": d["mv_y_hat"]}
+    finally:
+        # the picture files are finished (and their threads and streams drained) whatever the motion files did
+        planes = codec._decompress_gop_files_end(begun)
+    for (i, c), plane in zip(slots, planes):
+        frames_coded[i][c] = plane
+    if counters is not None:
+        for path, job in zip(paths, begun[0]):
+            counters[os.path.basename(path)] = {key: job[key] for key in ("symbols_decoded", "payload_bytes_used")}
+    return frames_coded, read, nbytes
+
+
 def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize=128, me_downsample=1, ll_order="plane",
                      luma_stage0=False):
     """Decode one GOP from the files encode_gop wrote into bin_folder, with nothing else from the encoder.
@@ -838,59 +937,14 @@ def decode_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psi
     Returns {"frames": [[Y, UV, None]] reconstructed (padded) pictures, "frames_coded": the decoded [L_t / H_t, L_tc /
     H_tc, mv_hat] entries decode_gop consumed}.  A missing, truncated or surplus-length file raises a ValueError that
     names it."""
-    import struct
     if ll_order not in LL_ORDERS:
         raise ValueError(f"ll_order must be one of {LL_ORDERS}")
-    pairs = gop_pairs(gop) if gop != 1 else []          # a lone picture (pmctf_seq): its two L files, no motion, no synthesis
-    stages = pairs[-1][0] + 1 if pairs else 0
-    pad_h = -(-pic_height // psize) * psize
-    pad_w = -(-pic_width // psize) * psize
-    files, names, slots = [], [], []
-
-    def picture(name, chroma, low, me_num, slot):
-        path = os.path.join(bin_folder, name)
-        data = _read_framed(path, 16)
-        h, w, n = struct.unpack(">III", data[:12])
-        want = (pic_height // 2, pic_width // 2, 2) if chroma else (pic_height, pic_width, 1)
-        if (h, w, n) != want:
-            raise ValueError(f"{path}: header says {n} plane(s) of {h}x{w}, expected {want[2]} of {want[0]}x{want[1]}")
-        files.append((data, chroma, low, me_num))
-        names.append(path)
-        slots.append(slot)
-
-    motion = []
-    for stage, i_ref, i_cur in pairs:
-        me_num = min(codec.num_me_stages - 1, stage)
-        picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
-        picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
-        path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
-        motion.append((stage, i_cur, me_num, path, _read_framed(path, 6)[6:]))
-    picture("0_main.bin", False, True, 0, (0, 0))
-    picture("0_C_main.bin", True, True, 0, (0, 1))
-
     with torch.no_grad():
-        begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, names)
-        frames_coded = [[None, None, None] for _ in range(gop)]
-        dpb, at_stage = None, None
-        try:
-            for stage, i_cur, me_num, path, string in motion:
-                if stage != at_stage:
-                    dpb, at_stage = {"mv_feature": None, "ref_mv_y": None}, stage
-                try:
-                    d = codec.decompress_mv(string, torch.float32, pad_h // me_downsample, pad_w // me_downsample, dpb,
-                                            stage_idx=me_num, q_index=q_index, me_downsample=me_downsample)
-                except (ValueError, RuntimeError) as e:
-                    raise ValueError(f"{path}: {e}") from e
-                frames_coded[i_cur][2] = d["mv_hat"]
-                dpb = {"mv_feature": d["mv_feature"], "ref_mv_y": d["mv_y_hat"]}
-        finally:
-            # the picture files are finished (and their threads and streams drained) whatever the motion files did
-            planes = codec._decompress_gop_files_end(begun)
-        for (i, c), plane in zip(slots, planes):
-            frames_coded[i][c] = plane
+        frames_coded, _, _ = _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample,
+                                             ll_order)
         coded = [list(fc) for fc in frames_coded]
         rec = decode_gop(codec, frames_coded, luma_stage0=luma_stage0)
-    return {"frames": rec, "frames_coded": coded, "stages": stages}
+    return {"frames": rec, "frames_coded": coded, "stages": int(round(math.log2(gop)))}
 
 
 def frames_to_samples(frames_rec, pic_height, pic_width, bitdepth=8):

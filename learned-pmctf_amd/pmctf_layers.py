@@ -78,9 +78,15 @@ def layer_bytes(bin_folder, level, motion_fill=False):
     summed over its GOPs.  ValueError naming a file that is missing."""
     check_level(level)
     _, gops = pmctf_gop.sequence_layout(bin_folder)
+    return files_bytes(bin_folder, ((k, layer_file_names(g[1], level, motion_fill)) for k, g in enumerate(gops)))
+
+
+def files_bytes(bin_folder, per_gop):
+    """the sizes of the files [(gop index, names)] of the sequence in bin_folder, summed; ValueError naming a file that is
+    missing"""
     total = 0
-    for k, g in enumerate(gops):
-        for name in layer_file_names(g[1], level, motion_fill):
+    for k, names in per_gop:
+        for name in names:
             path = os.path.join(bin_folder, pmctf_gop.gop_folder(k), name)
             try:
                 total += os.path.getsize(path)
@@ -90,120 +96,14 @@ def layer_bytes(bin_folder, level, motion_fill=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------- one GOP
-def _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, kk,
-                    motion_fill, spatial_level=0, counters=None):
-    """decode_gop_files up to the synthesis, on the files of layer_file_names alone -> (frames_coded with None where
-    nothing was read, names read, bytes read).  The header checks, the one picture batch and the motion loop under it are
-    those of pmctf_gop.decode_gop_files.  spatial_level=k: the planes of every picture file at spatial level k (the
-    motion fields stay as coded: reduce_motion).  counters: a dict that receives, per picture file name, what the engine
-    says it read of it: {"symbols_decoded", "payload_bytes_used"}."""
-    pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
-    return _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order,
-                           {i_cur for stage, _, i_cur in pairs if stage >= kk},
-                           {i_cur for stage, _, i_cur in pairs if stage >= kk or motion_fill}, spatial_level, counters)
-
-
-def _read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, pictures,
-                    motions, spatial_level=0, counters=None):
-    """the reader of _read_gop_layer and of pmctf_access: of the pairs of the GOP, in coding order, the two picture files of
-    those whose i_cur is in `pictures` and the motion file of those whose i_cur is in `motions`, then the two L files.
-    `motions` holds, of every stage it touches, the pairs from the stage's first on: the context runs pair to pair."""
-    import struct
-    import torch
-    pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
-    pad_h = -(-pic_height // psize) * psize
-    pad_w = -(-pic_width // psize) * psize
-    files, paths, slots, read = [], [], [], []
-    nbytes = 0
-
-    def picture(name, chroma, low, me_num, slot):
-        nonlocal nbytes
-        path = os.path.join(bin_folder, name)
-        data = pmctf_gop._read_framed(path, 16)
-        h, w, n = struct.unpack(">III", data[:12])
-        want = (pic_height // 2, pic_width // 2, 2) if chroma else (pic_height, pic_width, 1)
-        if (h, w, n) != want:
-            raise ValueError(f"{path}: header says {n} plane(s) of {h}x{w}, expected {want[2]} of {want[0]}x{want[1]}")
-        files.append((data, chroma, low, me_num))
-        paths.append(path)
-        slots.append(slot)
-        read.append(name)
-        nbytes += len(data)
-
-    motion = []
-    for stage, _, i_cur in pairs:
-        me_num = min(codec.num_me_stages - 1, stage)
-        if i_cur in pictures:
-            picture(f"{i_cur}.bin", False, False, me_num, (i_cur, 0))
-            picture(f"{i_cur}_C_main.bin", True, False, me_num, (i_cur, 1))
-        if i_cur not in motions:
-            continue
-        path = os.path.join(bin_folder, f"{i_cur}_mv.bin")
-        data = pmctf_gop._read_framed(path, 6)
-        motion.append((stage, i_cur, me_num, path, data[6:]))
-        read.append(f"{i_cur}_mv.bin")
-        nbytes += len(data)
-    picture(L_FILES[0], False, True, 0, (0, 0))
-    picture(L_FILES[1], True, True, 0, (0, 1))
-
-    begun = codec._decompress_gop_files_begin(files, psize, q_index, ll_order, paths, spatial_level=spatial_level)
-    frames_coded = [[None, None, None] for _ in range(gop)]
-    dpb, at_stage = None, None
-    try:
-        for stage, i_cur, me_num, path, string in motion:
-            if stage != at_stage:                         # the context restarts per stage: what makes the layers independent
-                dpb, at_stage = {"mv_feature": None, "ref_mv_y": None}, stage
-            try:
-                d = codec.decompress_mv(string, torch.float32, pad_h // me_downsample, pad_w // me_downsample, dpb,
-                                        stage_idx=me_num, q_index=q_index, me_downsample=me_downsample)
-            except (ValueError, RuntimeError) as e:
-                raise ValueError(f"{path}: {e}") from e
-            frames_coded[i_cur][2] = d["mv_hat"]
-            dpb = {"mv_feature": d["mv_feature"], "ref_mv_y": d["mv_y_hat"]}
-    finally:
-        # the picture files are finished (and their threads and streams drained) whatever the motion files did
-        planes = codec._decompress_gop_files_end(begun)
-    for (i, c), plane in zip(slots, planes):
-        frames_coded[i][c] = plane
-    if counters is not None:
-        for path, job in zip(paths, begun[0]):
-            counters[os.path.basename(path)] = {key: job[key] for key in ("symbols_decoded", "payload_bytes_used")}
-    return frames_coded, read, nbytes
-
-
 def reduce_motion(frames_coded, spatial_level):
     """the motion fields of a GOP's entries for planes of spatial level k: each reduced k times by ops.bilinear_down2(., 2.0),
     which halves the size and the vectors, so that every vector contributes; once per pair, shared by luma (as it is) and
-    chroma (inverse_MCTF(downscale=True) reduces it once more, as at full size).  Modifies and returns frames_coded."""
+    chroma (whose synthesis, downscale=True, reduces it once more, as at full size).  Modifies and returns frames_coded."""
     from pMCTF.hip import ops
     for entry in frames_coded:
         for _ in range(spatial_level if entry[2] is not None else 0):
             entry[2] = ops.bilinear_down2(entry[2].contiguous(), 2.0)
-    return frames_coded
-
-
-def _synthesis(codec, frames_coded, stages, down_to, snapshots=None):
-    """pmctf_gop.decode_gop's loop for the stages `stages - 1` .. `down_to`, on the GOP's own stage numbers; modifies and
-    returns frames_coded.  snapshots: a dict that receives, per level k in down_to..stages, the low-band pictures of that
-    level ([Y, UV, None] at the indices j * 2^k) as the list holds them once stage k is undone."""
-    def keep(k):
-        if snapshots is not None:
-            snapshots[k] = [list(frames_coded[j << k]) for j in range(len(frames_coded) >> k)]
-
-    keep(stages)
-    for stage_idx in reversed(range(down_to, stages)):
-        step = 2 ** stage_idx
-        me_num = min(codec.num_me_stages - 1, stage_idx)
-        for group_idx in reversed(range(len(frames_coded) >> (stage_idx + 1))):
-            i_ref = group_idx * 2 * step
-            L_t, L_tc, mv_ref = frames_coded[i_ref]
-            H_t, H_tc, mv_hat = frames_coded[i_ref + step]
-            assert mv_ref is None
-            ref, cur = codec.inverse_MCTF(L_t, H_t, mv_hat, stage_idx=me_num)
-            ref_c, cur_c = codec.inverse_MCTF(L_tc, H_tc, mv_hat, stage_idx=me_num, downscale=True)
-            frames_coded[i_ref] = [ref, ref_c, None]
-            frames_coded[i_ref + step] = [cur, cur_c, None]
-        keep(stage_idx)
     return frames_coded
 
 
@@ -241,37 +141,58 @@ def decode_gop_files_layer(codec, bin_folder, gop, pic_height, pic_width, q_inde
 def _decode_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, level, psize, me_downsample, ll_order,
                       motion_fill, spatial_level):
     """decode_gop_files_layer, and at spatial_level=k > 0 (pmctf_spatial) the same loop at 1/2^k of the size:
-    every picture file is decoded at spatial level k (nothing behind its level-k subbands is read from the stream), the
-    motion fields are reduced k times (reduce_motion) and the synthesis runs on the reduced planes; the pictures are padded
-    planes of 1/2^k of the size, to be cropped to pmctf_spatial.spatial_size.  A size that does not offer the level raises
-    the ValueError of spatial_size before any file is opened."""
+    _decode_gop_planned with the plan of a level.  Without motion_fill that is the full plan of a GOP of gop >> kk pictures
+    with every index shifted left by kk: the pairs of the stages S-1 .. kk and their files."""
+    def plan():
+        kk = min(level, gop_stages(gop))
+        pairs = pmctf_gop.gop_pairs(gop) if gop != 1 else []
+        pictures = {i_cur for stage, _, i_cur in pairs if stage >= kk}
+        if not motion_fill:
+            return pmctf_gop.synthesis_pairs(gop, kk), pictures, pictures, [], [j << kk for j in range(gop >> kk)]
+        fill = [i_cur for stage, _, i_cur in pairs if stage < kk]
+        return pmctf_gop.synthesis_pairs(gop), pictures, pictures | set(fill), fill, list(range(gop))
+
+    return _decode_gop_planned(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order,
+                               spatial_level, plan, level, motion_fill)[0]
+
+
+def _decode_gop_planned(codec, bin_folder, gop, pic_height, pic_width, q_index, psize, me_downsample, ll_order, spatial_level,
+                        plan, level=0, motion_fill=False, one_sided=False):
+    """The one per-GOP body under the temporal levels, motion_fill, the spatial levels and random access
+    (pmctf_access.decode_gop_files_frames): the argument checks, the size of the pictures, pmctf_gop's reader, the motion
+    reduced for the spatial level, the zero H planes, pmctf_gop's synthesis loop and the counters.
+    plan: called once the arguments are checked -> (pairs: [(stage, i_ref, i_cur, want_cur)] for pmctf_gop.synthesise,
+    pictures, motions: the sets of i_cur whose picture and motion files are read, fill: the i_cur whose H planes are zero
+    tensors, times: the offsets of the pictures that come out).
+    At spatial_level=k every picture file is decoded at spatial level k (nothing behind its level-k subbands is read from the
+    stream), the motion fields are reduced k times (reduce_motion) and the synthesis runs on the reduced planes; the pictures
+    are padded planes of 1/2^k of the size, to be cropped to pmctf_spatial.spatial_size.  A size that does not offer the
+    level raises the ValueError of spatial_size before any file is opened.
+    one_sided: pmctf_gop.synthesise's, for a plan with pairs whose want_cur is False.  -> (decode_gop_files_layer's dict, the plan's pairs)."""
     import torch
     _check_decode_args(level, motion_fill, ll_order, spatial_level)
+    if not any(one_sided is v for v in (True, False)):
+        raise ValueError(f"one_sided is True or False (got {one_sided!r})")
     size = pmctf_spatial.spatial_size(pic_height, pic_width, spatial_level)
     stages = gop_stages(gop)
-    kk = min(level, stages)
+    pairs, pictures, motions, fill, times = plan()
     counters = {}
     with torch.no_grad():
-        frames_coded, read, nbytes = _read_gop_layer(codec, bin_folder, gop, pic_height, pic_width, q_index, psize,
-                                                     me_downsample, ll_order, kk, motion_fill, spatial_level, counters)
+        frames_coded, read, nbytes = pmctf_gop._read_gop_files(codec, bin_folder, gop, pic_height, pic_width, q_index, psize,
+                                                               me_downsample, ll_order, pictures, motions, spatial_level,
+                                                               counters)
+        for i in motions - pictures - set(fill):          # decoded for the context of a later pair alone
+            frames_coded[i][2] = None
         reduce_motion(frames_coded, spatial_level)
-        if motion_fill:
-            for stage, _, i_cur in (pmctf_gop.gop_pairs(gop) if gop != 1 else []):
-                if stage < kk:
-                    frames_coded[i_cur][0] = torch.zeros_like(frames_coded[0][0])
-                    frames_coded[i_cur][1] = torch.zeros_like(frames_coded[0][1])
-            coded = [list(fc) for fc in frames_coded]
-            rec = pmctf_gop.decode_gop(codec, frames_coded)
-            times = list(range(gop))
-        else:
-            coded = [list(fc) for fc in frames_coded]
-            _synthesis(codec, frames_coded, stages, kk)
-            times = [j << kk for j in range(gop >> kk)]
-            rec = [frames_coded[t] for t in times]
-    return {"frames": rec, "times": times, "frames_coded": coded, "stages": stages, "files": read, "bytes_read": nbytes,
-            "spatial_level": spatial_level, "size": size,
+        for i in fill:
+            frames_coded[i][0] = torch.zeros_like(frames_coded[0][0])
+            frames_coded[i][1] = torch.zeros_like(frames_coded[0][1])
+        coded = [list(fc) for fc in frames_coded]
+        pmctf_gop.synthesise(codec, frames_coded, pairs, one_sided=one_sided)
+    return {"frames": [frames_coded[t] for t in times], "times": times, "frames_coded": coded, "stages": stages, "files": read,
+            "bytes_read": nbytes, "spatial_level": spatial_level, "size": size,
             "symbols_decoded": {n: c["symbols_decoded"] for n, c in counters.items()},
-            "payload_bytes_used": {n: c["payload_bytes_used"] for n, c in counters.items()}}
+            "payload_bytes_used": {n: c["payload_bytes_used"] for n, c in counters.items()}}, pairs
 
 
 # ------------------------------------------------------------------------------------------------------------ layer hashes
@@ -320,14 +241,11 @@ def read_layer_hashes(bin_folder):
     return record
 
 
-def write_layer_hashes(codec, bin_folder, hash_level=None):
-    """Decode bin_folder fully, GOP by GOP, and write bin_folder/layer_hashes.json: for every k from 1 to log2 of the
-    largest GOP the CRC-32 (pmctf_gop.picture_hashes) of every picture of layer k, taken out of the SAME synthesis as the
-    full-rate pictures, from the list as it stands once stage min(k, S) is undone.  Where picture_hashes.json is present
-    every GOP's full-rate pictures are checked against it first (PictureHashMismatch, nothing written): the layer record
-    is then anchored to the encoder's own reconstruction.  hash_level: that of picture_hashes.json by default, or "u8"
-    ("u16" above 8 bits) without one.  -> the path written."""
-    import torch
+def _open_for_hashes(codec, bin_folder, hash_level):
+    """what write_layer_hashes and pmctf_spatial.write_spatial_hashes do before their first GOP: the folder's layout and bit
+    depth, its recorded picture hashes where it has some, the hash level (that of the record by default, or "u8", "u16"
+    above 8 bits, without one), the refusal of an extracted folder and the header check against the codec
+    -> (header, gops, bitdepth, recorded or None, hash_level)"""
     G = pmctf_gop
     header, gops = G.sequence_layout(bin_folder)
     bitdepth = G.read_picture_format(bin_folder)
@@ -340,6 +258,40 @@ def write_layer_hashes(codec, bin_folder, hash_level=None):
     if os.path.exists(os.path.join(bin_folder, LAYER_EXTRACT)):
         raise ValueError(f"{os.path.join(bin_folder, LAYER_EXTRACT)}: an extracted folder cannot be decoded fully")
     G.check_sequence_header(header, G.codec_header_fields(codec))
+    return header, gops, bitdepth, recorded, hash_level
+
+
+def _gop_snapshots(codec, folder, size, h, w, q_index, psize, me_downsample, ll_order, spatial_level=0):
+    """one GOP decoded from all of its files at a spatial level -> {t: the pictures of temporal level t}, t = 0..S, out of
+    ONE synthesis (pmctf_gop.synthesise's snapshots)"""
+    coded, _, _ = pmctf_gop._read_gop_files(codec, folder, size, h, w, q_index, psize, me_downsample, ll_order,
+                                            spatial_level=spatial_level)
+    shots = {}
+    pmctf_gop.synthesise(codec, reduce_motion(coded, spatial_level), pmctf_gop.synthesis_pairs(size), snapshots=shots)
+    return shots
+
+
+def _check_full_rate(pictures, recorded, h, w, bitdepth, first, g, folder):
+    """GOP g's full-rate pictures against the folder's recorded picture hashes, where it has some: PictureHashMismatch"""
+    if recorded is None:
+        return
+    G = pmctf_gop
+    bad = G.compare_hash_records(G.picture_hashes(pictures, h, w, recorded["level"], bitdepth),
+                                 recorded["frames"][first:first + len(pictures)], first, gop=g, folder=folder)
+    if bad:
+        raise G.PictureHashMismatch(bad[0])
+
+
+def write_layer_hashes(codec, bin_folder, hash_level=None):
+    """Decode bin_folder fully, GOP by GOP, and write bin_folder/layer_hashes.json: for every k from 1 to log2 of the
+    largest GOP the CRC-32 (pmctf_gop.picture_hashes) of every picture of layer k, taken out of the SAME synthesis as the
+    full-rate pictures, from the list as it stands once stage min(k, S) is undone.  Where picture_hashes.json is present
+    every GOP's full-rate pictures are checked against it first (PictureHashMismatch, nothing written): the layer record
+    is then anchored to the encoder's own reconstruction.  hash_level: that of picture_hashes.json by default, or "u8"
+    ("u16" above 8 bits) without one.  -> the path written."""
+    import torch
+    G = pmctf_gop
+    header, gops, bitdepth, recorded, hash_level = _open_for_hashes(codec, bin_folder, hash_level)
     h, w = header["height"], header["width"]
     top = _max_level(gops)
     q_indexes = G.gop_q_indexes(header, len(gops))
@@ -347,18 +299,10 @@ def write_layer_hashes(codec, bin_folder, hash_level=None):
     with torch.no_grad():
         for g, (first, size, psize, me_downsample) in enumerate(gops):
             folder = os.path.join(bin_folder, G.gop_folder(g))
-            stages = gop_stages(size)
-            coded, _, _ = _read_gop_layer(codec, folder, size, h, w, q_indexes[g], psize, me_downsample,
-                                          header["ll_order"], 0, False)
-            shots = {}
-            _synthesis(codec, coded, stages, 0, shots)
-            if recorded is not None:
-                bad = G.compare_hash_records(G.picture_hashes(shots[0], h, w, recorded["level"], bitdepth),
-                                             recorded["frames"][first:first + size], first, gop=g, folder=folder)
-                if bad:
-                    raise G.PictureHashMismatch(bad[0])
+            shots = _gop_snapshots(codec, folder, size, h, w, q_indexes[g], psize, me_downsample, header["ll_order"])
+            _check_full_rate(shots[0], recorded, h, w, bitdepth, first, g, folder)
             for k in range(1, top + 1):
-                kk = min(k, stages)
+                kk = min(k, gop_stages(size))
                 for j, rec in enumerate(G.picture_hashes(shots[kk], h, w, hash_level, bitdepth)):
                     layers[str(k)].append(dict({key: int(rec[key]) for key in G.HASH_KEYS[hash_level]},
                                                index=first + (j << kk)))
@@ -430,6 +374,29 @@ def extract_layer(src_folder, dst_folder, level, motion_fill=False):
 
 
 # ------------------------------------------------------------------------------------------------------------ a sequence
+def spatial_picture_size(bin_folder, h, w, spatial_level, verify, coded_size_output, coded_format_output):
+    """-> pmctf_spatial.spatial_size of the folder's pictures, with the refusals of a spatial level that need no codec, for
+    LayerDecode and pmctf_access.FrameDecode: a size that does not offer the level, a display form the reduced pictures
+    cannot be given, verify=True without spatial_hashes.json"""
+    size = pmctf_spatial.spatial_size(h, w, spatial_level)
+    if spatial_level:
+        import pmctf_chroma
+        import pmctf_scale
+        source = pmctf_chroma.read_source_format(bin_folder)
+        other_format = source is not None and source["chroma_format"] != "420"
+        for name, differs, coded in ((pmctf_scale.DISPLAY_FORMAT, True, coded_size_output),
+                                     (pmctf_chroma.SOURCE_FORMAT, other_format, coded_format_output)):
+            path = os.path.join(bin_folder, name)
+            if os.path.exists(path) and differs and not coded:
+                raise ValueError(f"{path}: the folder's pictures are displayed in another form than they are coded in; "
+                                 f"spatial level {spatial_level} gives the coded form alone (ask for the coded "
+                                 f"size and the coded format), resampling a reduced picture is not done")
+        path = os.path.join(bin_folder, pmctf_spatial.SPATIAL_HASHES)
+        if verify is True and not os.path.exists(path):
+            raise ValueError(f"{path}: missing (write_spatial_hashes was not run on the folder)")
+    return size
+
+
 class LayerDecode(pmctf_gop.FullDecode):
     """pmctf_gop.decode_sequence_with at a temporal level: every GOP through decode_gop_files_layer, the pictures checked
     against picture_hashes.json where they are the full-rate ones (level 0, or a sequence of lone pictures: exactly
@@ -454,22 +421,8 @@ class LayerDecode(pmctf_gop.FullDecode):
         _check_against_extract(bin_folder, self.level, self.motion_fill)
 
     def picture_size(self, bin_folder, h, w, coded_size_output, coded_format_output):
-        self.size = pmctf_spatial.spatial_size(h, w, self.spatial_level)
-        if self.spatial_level:
-            import pmctf_chroma
-            import pmctf_scale
-            source = pmctf_chroma.read_source_format(bin_folder)
-            other_format = source is not None and source["chroma_format"] != "420"
-            for name, differs, coded in ((pmctf_scale.DISPLAY_FORMAT, True, coded_size_output),
-                                         (pmctf_chroma.SOURCE_FORMAT, other_format, coded_format_output)):
-                path = os.path.join(bin_folder, name)
-                if os.path.exists(path) and differs and not coded:
-                    raise ValueError(f"{path}: the folder's pictures are displayed in another form than they are coded in; "
-                                     f"spatial level {self.spatial_level} gives the coded form alone (ask for the coded "
-                                     f"size and the coded format), resampling a reduced picture is not done")
-            path = os.path.join(bin_folder, pmctf_spatial.SPATIAL_HASHES)
-            if self.verify is True and not os.path.exists(path):
-                raise ValueError(f"{path}: missing (write_spatial_hashes was not run on the folder)")
+        self.size = spatial_picture_size(bin_folder, h, w, self.spatial_level, self.verify, coded_size_output,
+                                         coded_format_output)
         return self.size
 
     def open(self, bin_folder, header, gops, verify):

@@ -127,17 +127,7 @@ def write_spatial_hashes(codec, bin_folder, hash_level=None):
     import torch
     import pmctf_gop as G
     import pmctf_layers as Y
-    header, gops = G.sequence_layout(bin_folder)
-    bitdepth = G.read_picture_format(bin_folder)
-    recorded = None
-    if os.path.exists(os.path.join(bin_folder, G.PICTURE_HASHES)):
-        recorded = G.read_picture_hashes(bin_folder, header["frame_num"])
-    if hash_level is None:
-        hash_level = recorded["level"] if recorded is not None else ("u16" if bitdepth > 8 else "u8")
-    G.check_hash_level(hash_level, bitdepth)
-    if os.path.exists(os.path.join(bin_folder, Y.LAYER_EXTRACT)):
-        raise ValueError(f"{os.path.join(bin_folder, Y.LAYER_EXTRACT)}: an extracted folder cannot be decoded fully")
-    G.check_sequence_header(header, G.codec_header_fields(codec))
+    header, gops, bitdepth, recorded, hash_level = Y._open_for_hashes(codec, bin_folder, hash_level)
     h, w = header["height"], header["width"]
     top = Y._max_level(gops)
     levels = range(1, max_spatial_level(h, w) + 1)
@@ -146,22 +136,15 @@ def write_spatial_hashes(codec, bin_folder, hash_level=None):
     with torch.no_grad():
         for g, (first, size, psize, me_downsample) in enumerate(gops):
             folder = os.path.join(bin_folder, G.gop_folder(g))
-            stages = Y.gop_stages(size)
-            read = lambda k: Y._read_gop_layer(codec, folder, size, h, w, q_indexes[g], psize, me_downsample,
-                                               header["ll_order"], 0, False, k)[0]
+            shots = lambda k: Y._gop_snapshots(codec, folder, size, h, w, q_indexes[g], psize, me_downsample,
+                                               header["ll_order"], k)
             if recorded is not None:
-                shots = {}
-                Y._synthesis(codec, read(0), stages, 0, shots)
-                bad = G.compare_hash_records(G.picture_hashes(shots[0], h, w, recorded["level"], bitdepth),
-                                             recorded["frames"][first:first + size], first, gop=g, folder=folder)
-                if bad:
-                    raise G.PictureHashMismatch(bad[0])
+                Y._check_full_rate(shots(0)[0], recorded, h, w, bitdepth, first, g, folder)
             for k in levels:
-                shots = {}
-                Y._synthesis(codec, Y.reduce_motion(read(k), k), stages, 0, shots)
+                at = shots(k)
                 for t in range(top + 1):
-                    tt = min(t, stages)
-                    for j, rec in enumerate(G.picture_hashes(shots[tt], h >> k, w >> k, hash_level, bitdepth)):
+                    tt = min(t, Y.gop_stages(size))
+                    for j, rec in enumerate(G.picture_hashes(at[tt], h >> k, w >> k, hash_level, bitdepth)):
                         layers[str(k)][str(t)].append(dict({key: int(rec[key]) for key in G.HASH_KEYS[hash_level]},
                                                            index=first + (j << tt)))
     record = {"format_version": SPATIAL_HASH_FORMAT_VERSION, "level": hash_level, "size": [w, h], "layers": layers}
