@@ -16,7 +16,8 @@ the host in float64.  A plane whose smaller side is 160 or less has no five scal
 The ctypes signatures of the five entries live here, with their only caller (pMCTF/hip/lib.py holds those of
 include/pmctf_hip.h).  Like the rest of the product path there is no CPU fallback: RuntimeError without a GPU.
 
-Out of scope: RGB-domain metrics above 8 bits, 4:0:0 and interlaced material, other metrics."""
+Out of scope: 4:0:0 and interlaced material, other metrics.  RGB above 8 bits: two gbrp10 / gbrp12 / gbrp16 files
+(pmctf_colour) are planar 4:4:4 files here, planes G, B, R; one RGB-domain MS-SSIM figure is not computed."""
 import ctypes as C
 import math
 import os

@@ -41,7 +41,13 @@ or a comma list of those, e.g. 37 or 1000:1100 or 0,8:12,40.  Only the GOPs that
 only the files the pictures depend on; the pictures are written in ascending order, the PNGs under their source indices, and
 each is checked against its own picture hash.  It composes with --png, --spatial-level, --coded-size-output,
 --coded-format-output, --output-layout and the verify flags, and is refused together with --temporal-level, --motion-fill
-and --compare.  The summary then holds the bytes of the files read and the number of GOPs opened."""
+and --compare.  The summary then holds the bytes of the files read and the number of GOPs opened.
+--rgb-output FILE --rgb-layout NAME (pmctf_colour) also writes every verified picture as RGB in that layout
+(rgb24, bgr24, rgba, bgra, rgb48, gbrp, gbrp10, gbrp12, gbrp16; of the folder's bit depth): the pictures as OUT would hold
+them, converted to 4:4:4 and then to RGB on the GPU by the colour description of the folder's colour_format.json
+(tools/encode_sequence.py --rgb-layout / --colour-matrix / --colour-range), or by --colour-matrix / --colour-range given
+here.  --png on a folder with a colour_format.json (or with the two options) writes its PNGs by that description instead of
+the harness's BT.601 full-range formulas.  Both compose with every decoder above; OUT may be left out."""
 import argparse
 import json
 import os
@@ -93,9 +99,19 @@ def main(argv=None):
                     help="after the decode, compare OUT with this file: per-plane PSNR and MS-SSIM in their own format")
     ap.add_argument("--frames", metavar="SPEC",
                     help="decode these pictures alone, from the files they depend on: N, A:B (half-open) or a comma list")
+    ap.add_argument("--rgb-output", metavar="FILE", help="also write every picture there as RGB (needs --rgb-layout)")
+    ap.add_argument("--rgb-layout", metavar="NAME", help="the layout of --rgb-output (pmctf_colour.LAYOUTS)")
+    ap.add_argument("--colour-matrix", choices=("bt601", "bt709", "bt2020"),
+                    help="convert to RGB by this matrix instead of the folder's colour_format.json (needs --colour-range)")
+    ap.add_argument("--colour-range", choices=("full", "limited"), help="the range that goes with --colour-matrix")
     ap.add_argument("bin_folder")
-    ap.add_argument("yuv_out", nargs="?", help="may be left out when --png is given")
+    ap.add_argument("yuv_out", nargs="?", help="may be left out when --png or --rgb-output is given")
     a = ap.parse_args(argv)
+    if (a.rgb_output is None) != (a.rgb_layout is None):
+        ap.error("--rgb-output and --rgb-layout go together")
+    if (a.colour_matrix is None) != (a.colour_range is None):
+        ap.error("--colour-matrix and --colour-range go together")
+    colour = None if a.colour_matrix is None else (a.colour_matrix, a.colour_range)
     layered = a.temporal_level is not None or a.motion_fill
     if layered and (a.temporal_level or 0) < 0:
         ap.error("--temporal-level is 0 or more")
@@ -103,7 +119,7 @@ def main(argv=None):
         ap.error("--spatial-level is 0 to 4")
     if a.motion_fill and a.verify is True:
         ap.error("--motion-fill output has no hashes: it cannot be combined with --verify")
-    if a.yuv_out is None and a.png is None:
+    if a.yuv_out is None and a.png is None and a.rgb_output is None:
         ap.error("give OUT.yuv, --png DIR or both")
     if a.compare is not None:
         if a.yuv_out is None:
@@ -132,6 +148,20 @@ def main(argv=None):
             ap.error(str(e))
         if a.yuv_out is None or pmctf_layout.pmctf_chroma.is_y4m(a.yuv_out):
             ap.error("--output-layout: needs an OUT file that is no .y4m (Y4M pictures are planar)")
+    import pmctf_colour
+    if a.rgb_layout is not None:
+        try:
+            pmctf_colour.check_rgb_layout(a.rgb_layout, "--rgb-layout")
+        except ValueError as e:
+            ap.error(str(e))
+    try:                                                 # a colour description in force: the decode goes through pmctf_colour
+        recorded = pmctf_colour.read_colour_format(a.bin_folder) if colour is None else None
+    except ValueError as e:
+        ap.error(str(e))
+    if a.rgb_output is not None and colour is None and recorded is None:
+        ap.error(f"--rgb-output: {os.path.join(a.bin_folder, pmctf_colour.COLOUR_FORMAT)} is missing; give --colour-matrix "
+                 f"and --colour-range")
+    as_rgb = (a.rgb_output is not None or a.png is not None) and (colour is not None or recorded is not None)
     import torch
     import pmctf_gop
     from pMCTF.models.video.pMCTF_L import pMCTF
@@ -161,7 +191,24 @@ def main(argv=None):
     net.update(force=True)
     with torch.no_grad():
         try:
-            if frames is not None:
+            if as_rgb:
+                if frames is not None:
+                    mode = pmctf_access.FrameDecode(frames, a.spatial_level or 0)
+                elif layered or a.spatial_level is not None:
+                    import pmctf_layers
+                    mode = pmctf_layers.LayerDecode(a.temporal_level or 0, a.motion_fill, a.spatial_level or 0)
+                else:
+                    mode = pmctf_gop.FullDecode()
+                try:
+                    out = pmctf_colour.decode_with(mode, net, a.bin_folder, a.yuv_out, a.device, a.png, a.verify,
+                                                   coded_size_output=a.coded_size_output,
+                                                   coded_format_output=a.coded_format_output, output_layout=a.output_layout,
+                                                   rgb_out=a.rgb_output, rgb_layout=a.rgb_layout, colour=colour)
+                except ValueError as e:
+                    if isinstance(e, pmctf_gop.PictureHashMismatch) or "rgb_layout" not in str(e):
+                        raise
+                    sys.exit(f"--rgb-layout: {e}")
+            elif frames is not None:
                 out = pmctf_access.decode_frames(net, a.bin_folder, a.yuv_out, frames, a.device, png_out=a.png,
                                                  verify=a.verify, spatial_level=a.spatial_level or 0,
                                                  coded_size_output=a.coded_size_output,

@@ -38,7 +38,13 @@ same of a raw planar file.  --chroma-loc then also tells the siting of the sourc
 BIN_FOLDER/source_format.json keeps the source's format and frame rate, to which tools/decode_sequence.py converts back.
 --pixel-layout NAME [--pitch BYTES] [--luma-rows N] (pmctf_layout): SOURCE is a raw file of pictures in that
 layout (nv12, nv21, nv16, p010..p216, yuyv, uyvy, y210..y216, v210), unpacked on the GPU before anything else; the layout
-says the bit depth and the chroma format, and BIN_FOLDER is the one the planar file of the same pictures codes to."""
+says the bit depth and the chroma format, and BIN_FOLDER is the one the planar file of the same pictures codes to.
+--rgb-layout NAME [--colour-matrix bt601|bt709|bt2020] [--colour-range full|limited] (pmctf_colour): SOURCE is a
+raw file of RGB pictures in that layout (rgb24, bgr24, rgba, bgra, rgb48, gbrp, gbrp10, gbrp12, gbrp16), converted on the
+GPU to 4:4:4 YCbCr by that description (default bt709 limited) and coded as that planar 4:4:4 source is; BIN_FOLDER also
+gets colour_format.json, by which tools/decode_sequence.py --rgb-output and --png convert back.  With a folder of PNGs the
+two colour options convert the PNGs the same way (without them: the harness's BT.601 full-range float formulas); with a
+YCbCr source they only record the description."""
 import argparse
 import os
 import sys
@@ -99,15 +105,40 @@ def main(argv=None):
     ap.add_argument("--pitch", type=int, metavar="BYTES", help="--pixel-layout: bytes from one row to the next (default: tight)")
     ap.add_argument("--luma-rows", type=int, metavar="N",
                     help="--pixel-layout, semi-planar: rows of the luma plane (default: the height)")
+    ap.add_argument("--rgb-layout", metavar="NAME", help="SOURCE holds RGB pictures in this layout (pmctf_colour.LAYOUTS)")
+    ap.add_argument("--colour-matrix", choices=("bt601", "bt709", "bt2020"),
+                    help="the matrix between RGB and YCbCr (default bt709 once --rgb-layout or --colour-range is given)")
+    ap.add_argument("--colour-range", choices=("full", "limited"),
+                    help="the range of the YCbCr pictures (default limited once --rgb-layout or --colour-matrix is given)")
     ap.add_argument("source", help=".yuv or .y4m file, or folder of PNGs")
     ap.add_argument("bin_folder")
     a = ap.parse_args(argv)
     import pmctf_chroma
+    import pmctf_colour
     import pmctf_layout
     import pmctf_scale
     y4m = pmctf_chroma.is_y4m(a.source) and not os.path.isdir(a.source)
     unpack = None
-    if a.pixel_layout is None:
+    colour = None
+    if a.colour_matrix is not None or a.colour_range is not None or a.rgb_layout is not None:
+        colour = (a.colour_matrix or pmctf_colour.DEFAULT_COLOUR[0], a.colour_range or pmctf_colour.DEFAULT_COLOUR[1])
+    if a.rgb_layout is not None:
+        if y4m or os.path.isdir(a.source):
+            ap.error("--rgb-layout: for a raw file; a .y4m is YCbCr and PNGs are rgb24 by themselves")
+        if a.pixel_layout is not None:
+            ap.error("--rgb-layout: cannot be combined with --pixel-layout, which describes YCbCr pictures")
+        if a.width is None or a.height is None:
+            ap.error("--width and --height are required with --rgb-layout")
+        try:
+            unpack = pmctf_colour.RgbUnpacker(a.rgb_layout, a.width, a.height, colour, what="--rgb-layout")
+        except ValueError as e:
+            ap.error(f"--rgb-layout: {e}")
+        if a.bitdepth not in (None, unpack.bitdepth):
+            ap.error(f"--bitdepth {a.bitdepth}: --rgb-layout {a.rgb_layout} has {unpack.bitdepth}")
+        if a.chroma_format not in (None, "444"):
+            ap.error(f"--chroma-format {a.chroma_format}: --rgb-layout pictures are converted to 444")
+        a.bitdepth = unpack.bitdepth
+    elif a.pixel_layout is None:
         for opt in ("pitch", "luma_rows"):
             if getattr(a, opt) is not None:
                 ap.error(f"--{opt.replace('_', '-')}: only with --pixel-layout")
@@ -205,7 +236,8 @@ def main(argv=None):
         if unpack is not None:
             available, rest = divmod(os.path.getsize(a.source), unpack.frame_bytes)
             if rest:
-                ap.error(f"{a.source}: not a whole number of {a.pixel_layout} pictures of {unpack.frame_bytes} bytes")
+                ap.error(f"{a.source}: not a whole number of {a.pixel_layout or a.rgb_layout} pictures of "
+                         f"{unpack.frame_bytes} bytes")
         elif converted:
             try:
                 available = len(pmctf_chroma.PlanarReader(a.source, width, height, 0, a.bitdepth, a.chroma_format))
@@ -239,24 +271,24 @@ def main(argv=None):
     os.makedirs(a.bin_folder, exist_ok=True)
     common = dict(src_format=src_format, decoded_frame_path=a.decoded_frames, msssim=a.msssim, picture_hash=a.picture_hash,
                   bitdepth=a.bitdepth, coded_size=coded_size, chroma_loc=a.chroma_loc, chroma_format=a.chroma_format)
-    common.update(pixel_layout=a.pixel_layout, pitch=a.pitch, luma_rows=a.luma_rows)
+    common.update(pixel_layout=a.pixel_layout, pitch=a.pitch, luma_rows=a.luma_rows, rgb_layout=a.rgb_layout, colour=colour)
     with torch.no_grad():
         if fixed:
-            out = pmctf_layout.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
+            out = pmctf_colour.encode_sequence(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder, a.device,
                                              keep_gops=True, **common)
         else:
             import pmctf_seq
             cuts = dict(structure=a.structure, hd_min=pmctf_seq.HD_MIN if a.hd_min is None else a.hd_min,
                         mad_min=pmctf_seq.MAD_MIN if a.mad_min is None else a.mad_min)
             if rate is not None:
-                out = pmctf_layout.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
+                out = pmctf_colour.encode_sequence_rate(net, a.source, width, height, frames, a.gop, a.bitrate, a.fps,
                                                        a.bin_folder, a.device, **cuts, **common, **rate)
                 for k, r in enumerate(out["rate"]):
                     print(f"GOP {k}: q_index {r['q_index']}, {r['bits']} bits of {r['budget']}"
                           f"{'' if r['fits'] else ' (does not fit)'}, {len(r['trials'])} trial(s), credit {r['credit']}",
                           file=sys.stderr)
             else:
-                out = pmctf_layout.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
+                out = pmctf_colour.encode_sequence_gops(net, a.source, width, height, frames, a.gop, a.q_index, a.bin_folder,
                                                         a.device, **cuts, **common)
             if "cuts" in out:
                 print(f"scene cuts at pictures {out['cuts']}", file=sys.stderr)
